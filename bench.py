@@ -1,6 +1,6 @@
 """bench.py -- MSV scoring throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg3]
+    python bench.py --gpus N --steps K --warmup W [--config cfg3] [--dump-outputs DIR] [--full]
     (N > 1, one process per GPU: under torch.distributed.run WORLD_SIZE must equal N; started
     without it, bench.py runs `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
     child process before touching torch or the GPU and exits with its status)
@@ -15,12 +15,19 @@ data-path collective.
       contiguous shards (distributed.shard_bounds == msv_shard_bounds); the RCCL gather of the
       scores to every rank is part of every timed step.
 
-Rank 0 prints ONE JSON line with the contract keys plus:
+A plain run does what the headline figure needs and no more: set-up, untimed steps until the GPU clock
+has settled (CLOCK_SETTLE_S) and the W warm-up steps, the K timed steps, --dump-outputs DIR (the scores of
+the last timed step as DIR/scores.npy; the inputs are seeded, so two builds compare score for score), and
+the result line.  Everything else runs only with --full: the host end-to-end paths and the two-stream pass
+(before the timed steps), the in-kernel clock, cfg2's latency floor, the Viterbi stage, the CPU baseline,
+and the bitwise comparison of all of their scores with the timed steps'.
+
+Rank 0 prints ONE JSON line with the contract keys (ms_per_step = the timed window / K) plus:
   roofline     -- the dominant kernel against the fp32 VALU issue roofline:
                   3 fp32 ops (add, max, max) per cell, cells = residues x LENG;
                   peak = 256 CU x 128 lanes x 2.4 GHz = 78.64 T ops/s (non-FMA VALU);
                   achieved from the kernel's HIP-event time on the stream it runs on.
-  cpu_baseline -- the reference's OWN run_on_sequence (oracle/_ref, "reference") or the oracle
+  cpu_baseline -- (--full) the reference's OWN run_on_sequence (oracle/_ref, "reference") or the oracle
                   restatement ("port") on the host cores, on a bounded leading sample of the same
                   batch, timed in this run; its scores are also compared bitwise with the GPU's.
 """
@@ -65,6 +72,14 @@ def parse():
     ap.add_argument("--warmup", type=int, default=12,
                     help="untimed steps; the MI355X clock ramps over the first ~10 launches (3.8 -> 3.0 ms)")
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the host end-to-end "
+                         "paths, the two-stream pass, the in-kernel clock, cfg2's latency floor, the Viterbi "
+                         "stage and the CPU baseline (--cpu-seconds, --cpu-threads, --no-cpu, --no-viterbi and "
+                         "--no-clock act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the scores of the last timed step to DIR/scores.npy "
+                         "(float32; with more than one rank, DIR/scores_rank<r>.npy per rank)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample duration")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may run on")
     ap.add_argument("--no-cpu", action="store_true")
@@ -182,6 +197,7 @@ def cpu_baseline(profile_path, codes, offsets, gpu_scores, target_s, threads):
     }
 
 
+CLOCK_SETTLE_S = 1.0  # a plain run's untimed steps before the warm-up ones, until the GPU clock has ramped from idle
 VIT_WARMUP = 20  # untimed Viterbi launches before the timed ones
 VIT_OPS_PER_CELL = 14  # fp32 ops per Viterbi DP cell (msv.h): M 3 adds + 3 max + 1 add, I 2 + 1, D 2 + 1, E 1
 
@@ -547,7 +563,7 @@ def main(args=None):
     native.msv_debug_set_clock_stamps.argtypes = [C.c_void_p, C.c_void_p]
     native.msv_debug_grid_waves.argtypes = [C.c_void_p]
 
-    def step(ev=None, stamps=None):
+    def step(ev=None, stamps=None, gather=True):
         order_ptr = None
         if not args.no_order:
             engine.order_longest_first(d_off.data_ptr(), n, d_order.data_ptr(), sh)
@@ -557,87 +573,105 @@ def main(args=None):
         # stamps: this launch runs the plan's CLOCK twin, every wave writing realtime + shader-clock stamps
         native.msv_debug_set_clock_stamps(engine._p, None if stamps is None else stamps.data_ptr())
         engine.score_batch_device(d_res.data_ptr(), residues, d_off.data_ptr(), n, d_scores.data_ptr(), order_ptr, sh)
-        if gathered is not None and world > 1:  # cfg4: the RCCL gather of the scores is part of the step
+        if gather and gathered is not None and world > 1:  # cfg4: the RCCL gather of the scores is part of the step
             with torch.cuda.stream(stream):
                 src = d_scores if backend == "nccl" else d_scores.cpu()
                 dist.all_gather_into_tensor(gathered, src)
 
-    # Informational end-to-end rates first (their calls also bring the GPU clock up before the timed
-    # loop): host buffers -> msv_score_batch (H2D pipelined under the kernels, scores D2H), warm.
-    # Pinned = residues in page-locked memory (SURVEY 8(d)'s headline shape); pageable = plain numpy.
-    pinned_codes = torch.from_numpy(codes).pin_memory().numpy()
+    def informational_passes():
+        # Informational end-to-end rates first (their calls also bring the GPU clock up before the timed
+        # loop): host buffers -> msv_score_batch (H2D pipelined under the kernels, scores D2H), warm.
+        # Pinned = residues in page-locked memory (SURVEY 8(d)'s headline shape); pageable = plain numpy.
+        pinned_codes = torch.from_numpy(codes).pin_memory().numpy()
 
-    def host_rate(src, out, settle_s=0.0):
-        t = time.perf_counter()  # warm; the first call also settles the GPU clock (ramps from idle)
-        while True:
-            engine.score_batch(codes=src, offsets=offsets, out=out)
-            if time.perf_counter() - t >= settle_s:
-                break
-        for _ in range(3):
-            engine.score_batch(codes=src, offsets=offsets, out=out)
-        t = time.perf_counter()
-        for _ in range(args.steps):
-            engine.score_batch(codes=src, offsets=offsets, out=out)
-        return residues * args.steps / (time.perf_counter() - t) / 1e6, out.copy()
+        def host_rate(src, out, settle_s=0.0):
+            t = time.perf_counter()  # warm; the first call also settles the GPU clock (ramps from idle)
+            while True:
+                engine.score_batch(codes=src, offsets=offsets, out=out)
+                if time.perf_counter() - t >= settle_s:
+                    break
+            for _ in range(3):
+                engine.score_batch(codes=src, offsets=offsets, out=out)
+            t = time.perf_counter()
+            for _ in range(args.steps):
+                engine.score_batch(codes=src, offsets=offsets, out=out)
+            return residues * args.steps / (time.perf_counter() - t) / 1e6, out.copy()
 
-    # pinned: residues AND scores in page-locked host memory; pageable: both plain numpy arrays
-    host_pinned, pinned_scores = host_rate(pinned_codes, torch.empty(n, dtype=torch.float32).pin_memory().numpy(),
-                                           settle_s=0.5)
-    host_pageable, pageable_scores = host_rate(codes, np.zeros(n, np.float32))
-    # pinned residues are read in place by the kernel (zero-copy); the same call through the copy pipeline:
-    _native.lib().msv_debug_set_zero_copy.argtypes = [C.c_void_p, C.c_int]
-    _native.lib().msv_debug_set_zero_copy(engine._p, 0)
-    host_pinned_copy, copy_scores = host_rate(pinned_codes, torch.empty(n, dtype=torch.float32).pin_memory().numpy())
-    _native.lib().msv_debug_set_zero_copy(engine._p, 1)
+        # pinned: residues AND scores in page-locked host memory; pageable: both plain numpy arrays
+        host_pinned, pinned_scores = host_rate(pinned_codes, torch.empty(n, dtype=torch.float32).pin_memory().numpy(),
+                                               settle_s=0.5)
+        host_pageable, pageable_scores = host_rate(codes, np.zeros(n, np.float32))
+        # pinned residues are read in place by the kernel (zero-copy); the same call through the copy pipeline:
+        _native.lib().msv_debug_set_zero_copy.argtypes = [C.c_void_p, C.c_int]
+        _native.lib().msv_debug_set_zero_copy(engine._p, 0)
+        host_pinned_copy, copy_scores = host_rate(pinned_codes, torch.empty(n, dtype=torch.float32).pin_memory().numpy())
+        _native.lib().msv_debug_set_zero_copy(engine._p, 1)
 
-    # Stream of batches (serving): msv_score_batch_async keeps three calls in flight, so the H2D of the
-    # next calls runs back to back under the current call's kernel; scores land in pinned host arrays.
-    outs = [torch.empty(n, dtype=torch.float32).pin_memory().numpy() for _ in range(3)]
+        # Stream of batches (serving): msv_score_batch_async keeps three calls in flight, so the H2D of the
+        # next calls runs back to back under the current call's kernel; scores land in pinned host arrays.
+        outs = [torch.empty(n, dtype=torch.float32).pin_memory().numpy() for _ in range(3)]
 
-    def streamed_rate():
-        for _ in range(3):
-            engine.wait(engine.score_batch_async(pinned_codes, offsets, outs[0]))
-        t = time.perf_counter()
-        inflight = []
+        def streamed_rate():
+            for _ in range(3):
+                engine.wait(engine.score_batch_async(pinned_codes, offsets, outs[0]))
+            t = time.perf_counter()
+            inflight = []
+            for k in range(args.steps):
+                inflight.append(engine.score_batch_async(pinned_codes, offsets, outs[k % 3]))
+                if len(inflight) == 3:
+                    engine.wait(inflight.pop(0))
+            for tk in inflight:
+                engine.wait(tk)
+            return residues * args.steps / (time.perf_counter() - t) / 1e6
+
+        host_streamed = streamed_rate()
+        streamed_scores = outs[(args.steps - 1) % 3].copy()
+
+        # Information, never `value` (run BEFORE the timed steps, so those stay the last K MSV dispatches for
+        # tools/rocprof_window.py): K steps as a stream of resident batches alternating over two streams, so
+        # each step's blocks take the CUs that the previous step's drain tail frees (what
+        # msv_score_batch_async does for host batches).  Every step still sorts and scores its whole batch.
+        stream_b = torch.cuda.Stream(dev)
+        d_scores_b = torch.full_like(d_scores, float("nan"))
+        d_order_b = torch.empty_like(d_order)
+        lanes = [(stream, d_scores, d_order), (stream_b, d_scores_b, d_order_b)]
+
+        def step_two_streams(k):
+            st, sc, od = lanes[k % 2]
+            order_ptr = None
+            if not args.no_order:
+                engine.order_longest_first(d_off.data_ptr(), n, od.data_ptr(), st.cuda_stream)
+                order_ptr = od.data_ptr()
+            engine.score_batch_device(d_res.data_ptr(), residues, d_off.data_ptr(), n, sc.data_ptr(), order_ptr,
+                                      st.cuda_stream)
+
+        for k in range(2):
+            step_two_streams(k)
+        torch.cuda.synchronize(dev)
+        tb = time.perf_counter()
         for k in range(args.steps):
-            inflight.append(engine.score_batch_async(pinned_codes, offsets, outs[k % 3]))
-            if len(inflight) == 3:
-                engine.wait(inflight.pop(0))
-        for tk in inflight:
-            engine.wait(tk)
-        return residues * args.steps / (time.perf_counter() - t) / 1e6
+            step_two_streams(k)
+        torch.cuda.synchronize(dev)
+        two_stream_rate = residues * args.steps / (time.perf_counter() - tb) / 1e6
+        engine.check(sh)
+        two_stream_scores = (d_scores[:n].cpu().numpy().copy(), d_scores_b[:n].cpu().numpy().copy())
+        return {"host_pinned": host_pinned, "host_pageable": host_pageable, "host_pinned_copy": host_pinned_copy,
+                "host_streamed": host_streamed, "two_stream_rate": two_stream_rate,
+                "scores": [pinned_scores, pageable_scores, copy_scores, streamed_scores, *two_stream_scores]}
 
-    host_streamed = streamed_rate()
-    streamed_scores = outs[(args.steps - 1) % 3].copy()
-
-    # Information, never `value` (run BEFORE the timed steps, so those stay the last K MSV dispatches for
-    # tools/rocprof_window.py): K steps as a stream of resident batches alternating over two streams, so
-    # each step's blocks take the CUs that the previous step's drain tail frees (what
-    # msv_score_batch_async does for host batches).  Every step still sorts and scores its whole batch.
-    stream_b = torch.cuda.Stream(dev)
-    d_scores_b = torch.full_like(d_scores, float("nan"))
-    d_order_b = torch.empty_like(d_order)
-    lanes = [(stream, d_scores, d_order), (stream_b, d_scores_b, d_order_b)]
-
-    def step_two_streams(k):
-        st, sc, od = lanes[k % 2]
-        order_ptr = None
-        if not args.no_order:
-            engine.order_longest_first(d_off.data_ptr(), n, od.data_ptr(), st.cuda_stream)
-            order_ptr = od.data_ptr()
-        engine.score_batch_device(d_res.data_ptr(), residues, d_off.data_ptr(), n, sc.data_ptr(), order_ptr,
-                                  st.cuda_stream)
-
-    for k in range(2):
-        step_two_streams(k)
-    torch.cuda.synchronize(dev)
-    tb = time.perf_counter()
-    for k in range(args.steps):
-        step_two_streams(k)
-    torch.cuda.synchronize(dev)
-    two_stream_rate = residues * args.steps / (time.perf_counter() - tb) / 1e6
-    engine.check(sh)
-    two_stream_scores = (d_scores[:n].cpu().numpy().copy(), d_scores_b[:n].cpu().numpy().copy())
+    info_passes = host_pinned = host_pageable = host_pinned_copy = host_streamed = two_stream_rate = None
+    if args.full:
+        info_passes = informational_passes()
+        host_pinned, host_pageable, host_pinned_copy, host_streamed, two_stream_rate = (
+            info_passes[k] for k in ("host_pinned", "host_pageable", "host_pinned_copy", "host_streamed",
+                                     "two_stream_rate"))
+    else:
+        # `value` is the rate at the settled GPU clock, which ramps from idle (what the informational passes'
+        # launches do for a --full run): untimed steps for CLOCK_SETTLE_S before the warm-up steps.
+        t = time.perf_counter()
+        while time.perf_counter() - t < CLOCK_SETTLE_S:  # per rank by the clock, so without the collective
+            step(gather=False)
+            torch.cuda.synchronize(dev)
 
     for _ in range(args.warmup):
         step()
@@ -662,13 +696,17 @@ def main(args=None):
     # The timed launches' own scores, before the CLOCK twin below writes the same buffer again: these are
     # what every equality check and the CPU baseline compare against.
     timed_scores = d_scores[:n].cpu().numpy().copy()
+    if args.dump_outputs:  # what a caller of the timed path receives from its last step: this rank's scores
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy" if world == 1 else f"scores_rank{rank}.npy"),
+                timed_scores.astype(np.float32, copy=False))
     # Clock under this load: `steps` more steps right after the timed window, the same batch and plan, run
     # by the plan's CLOCK twin (msv_kernel_impl.h clock_fn: the production kernel whose per-wave stamps also
     # record s_memtime -- one tick per shader cycle -- beside s_memrealtime at 100 MHz; a separate
     # instantiation, so the timed kernel's ISA is untouched).  clock = sum of ticks / sum of realtime over
     # the waves of a launch, median over the launches; the twin's own kernel time is reported beside it.
     clock = None
-    if not args.no_clock:
+    if args.full and not args.no_clock:
         nwaves = int(native.msv_debug_grid_waves(engine._p))
         bufs = [torch.zeros(nwaves * 6, dtype=torch.int64, device=dev) for _ in range(args.steps)]
         cev = [(hip_event(), hip_event()) for _ in range(args.steps)]
@@ -721,18 +759,18 @@ def main(args=None):
         gather_ms = (time.perf_counter() - g0) * 1e3
 
     scores = timed_scores
-    twin_scores = d_scores[:n].cpu().numpy()  # the CLOCK twin's launches (after the timed window)
-    twin_equal = bool(np.array_equal(twin_scores.view(np.uint32), scores.view(np.uint32)))
-    d_scores[:n].copy_(torch.from_numpy(timed_scores))  # the Viterbi stage filters the timed launches' scores
-    ok = bool(np.all(np.isfinite(scores)))
-    ok = ok and bool(np.array_equal(pinned_scores.view(np.uint32), scores.view(np.uint32)))
-    ok = ok and bool(np.array_equal(pageable_scores.view(np.uint32), scores.view(np.uint32)))
-    ok = ok and bool(np.array_equal(streamed_scores.view(np.uint32), scores.view(np.uint32)))
-    ok = ok and all(bool(np.array_equal(x.view(np.uint32), scores.view(np.uint32))) for x in two_stream_scores)
-    ok = ok and bool(np.array_equal(copy_scores.view(np.uint32), scores.view(np.uint32)))
-    if gathered is not None and world > 1:  # every shard landed at its rows of the gathered set
-        g = gathered.cpu().numpy().reshape(world, -1)
-        ok = ok and bool(np.array_equal(g[rank, :n].view(np.uint32), scores.view(np.uint32)))
+    finite = bool(np.all(np.isfinite(scores)))
+    ok = twin_equal = None
+    if args.full:
+        twin_scores = d_scores[:n].cpu().numpy()  # the CLOCK twin's launches (after the timed window)
+        twin_equal = bool(np.array_equal(twin_scores.view(np.uint32), scores.view(np.uint32)))
+        d_scores[:n].copy_(torch.from_numpy(timed_scores))  # the Viterbi stage filters the timed launches' scores
+        # the host paths (pinned, pageable, copy pipeline, streamed) and both lanes of the two-stream pass
+        ok = finite and all(bool(np.array_equal(x.view(np.uint32), scores.view(np.uint32)))
+                            for x in info_passes["scores"])
+        if gathered is not None and world > 1:  # every shard landed at its rows of the gathered set
+            g = gathered.cpu().numpy().reshape(world, -1)
+            ok = ok and bool(np.array_equal(g[rank, :n].view(np.uint32), scores.view(np.uint32)))
     value = residues_all * args.steps / elapsed / 1e6  # M residues / s, whole job
     gcups = value * 1e6 * leng / 1e9
 
@@ -812,7 +850,9 @@ def main(args=None):
             },
             "gather_ms": gather_ms,
             "per_rank": per_rank,
-            "end_to_end": {
+            "full": args.full,
+            "scores_finite": finite,
+            "end_to_end": None if not args.full else {
                 "host_pinned_M_residues_s": round(host_pinned, 1),
                 "host_pageable_M_residues_s": round(host_pageable, 1),
                 "host_pinned_copy_pipeline_M_residues_s": round(host_pinned_copy, 1),
@@ -838,15 +878,15 @@ def main(args=None):
                               "the two-stream pass and cpu_baseline.bitwise_equal_to_gpu compare against them",
             "clock_twin_scores_bitwise_equal": twin_equal,
         }
-        if args.config == "cfg2":  # the latency-bound config: its measured floor beside the kernel
+        if args.full and args.config == "cfg2":  # the latency-bound config: its measured floor beside the kernel
             result["latency_ceiling"] = latency_ceiling(engine, dev, sh, n, lmax,
                                                         int(np.diff(offsets.astype(np.int64)).max()), kernel_ms,
                                                         hip_event, hip_elapsed_ms)
-        if not args.no_viterbi:
+        if args.full and not args.no_viterbi:
             result["viterbi_stage"] = viterbi_stage(args, engine, prof_path, dev, stream, d_res, residues, d_off, n,
                                                     d_scores, None if args.no_order else d_order, codes, offsets,
                                                     lmax, leng, hip_event, hip_elapsed_ms)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline(prof_path, codes, offsets, scores, args.cpu_seconds,
                                                   cpu_threads(args.cpu_threads))
             cb = result["cpu_baseline"]

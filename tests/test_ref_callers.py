@@ -1,5 +1,5 @@
 """The drop-in proof of SURVEY 8(b): the reference's OWN callers of the MSV path, compiled unchanged against this
-library (tests/ref_callers/Makefile: the sources read where they lie under /root/reference, the forwarding headers
+library (oracle/ref_callers/Makefile: the sources read where they lie under /root/reference, the forwarding headers
 include/drop_in/{MSV_HMM,Profile_HMM,FASTA_protein_sequences}.hpp, libmsv_hip.so), run the way the reference runs
 them: from a build/<subdir> working directory with ../profile_HMMs and ../FASTA_files beside it
 (compile_clang_in_build_dir.sh:4-7).
@@ -11,9 +11,11 @@ them: from a build/<subdir> working directory with ../profile_HMMs and ../FASTA_
                                          1e-4 as the reference asserts (test_MSV.cpp:9-31)
   benchmark_MSV, benchmark_MSV_1400      GPU: rc 0, every "best time" line printed (benchmark_helper.hpp:40-41)
 
-The binaries are built in the build container (build() or `make -C tests/ref_callers`, which needs
-/root/reference) and travel to the GPU box with the tree; the recipe fails the build if any reference header
-other than benchmark_helper.hpp was compiled in, and the dependency lists it writes are checked again here."""
+The binaries are built where the reference tree exists (build() or `make -C oracle/ref_callers`, which needs
+/root/reference) into oracle/_ref/ref_callers, beside the reference's CPU path, and reach a GPU machine with
+oracle/_ref; the recipe fails the build if any reference header other than benchmark_helper.hpp was compiled in,
+and the dependency lists it writes (this library's headers relative to the repository root) are checked again
+here."""
 import os
 import re
 import subprocess
@@ -23,16 +25,16 @@ import pytest
 
 from oracle_lib import ROOT
 
-BIN = os.path.join(ROOT, "build", "ref_callers")
+BIN = os.path.join(ROOT, "oracle", "_ref", "ref_callers")
 REF = "/root/reference"
 PROFILES = sorted(f for f in os.listdir(os.path.join(ROOT, "data", "profile_HMMs")) if f.endswith(".hmm"))
 
 
 def binary(name):
     if os.path.isdir(os.path.join(REF, "algorithms")):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "ref_callers")], check=True)
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle", "ref_callers")], check=True)
     path = os.path.join(BIN, name)
-    assert os.path.exists(path), f"{path} missing: build it with `make -C tests/ref_callers` where /root/reference exists"
+    assert os.path.exists(path), f"{path} missing: build it with `make -C oracle/ref_callers` where /root/reference exists"
     return path
 
 
@@ -56,8 +58,10 @@ def test_only_the_library_headers_were_compiled_in(name):
     assert all(d.endswith("/benchmark_helper.hpp") for d in ref_headers), ref_headers
     for h in ("MSV_HMM.hpp", "Profile_HMM.hpp", "FASTA_protein_sequences.hpp"):
         if any(d.endswith("/" + h) for d in deps):
-            assert os.path.join(ROOT, "include", "drop_in", h) in deps
-    assert os.path.join(ROOT, "include", "msv_hmm.hpp") in deps
+            assert os.path.join("include", "drop_in", h) in deps
+    assert os.path.join("include", "msv_hmm.hpp") in deps
+    lib_headers = [d for d in deps if d.endswith((".hpp", ".h")) and not d.startswith(("/usr/", REF))]
+    assert lib_headers and all(d.startswith("include/") for d in lib_headers), lib_headers
 
 
 @pytest.mark.parametrize("name", ["test_hmm_parsing", "test_fasta_parsing"])

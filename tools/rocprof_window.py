@@ -8,9 +8,9 @@ Dispatches are filtered on ONE exact kernel: --variant maps the library's varian
 zero-copy twins that bench.py's informational host paths launch (`..., 2>`) are never averaged in or
 used as the label.  A --kernel substring that matches more than one distinct kernel is an error.
 
-bench.py launches the MSV kernel for its informational host paths first, then W warmup and K timed
-steps, and nothing after them (with --no-cpu), so its timed window is the LAST K dispatches of the
-resident kernel.  rocprofv3 --stats averages all dispatches, including the host-path pieces and the
+bench.py launches the MSV kernel for its clock-settling steps (with --full: for its informational host
+paths) first, then W warmup and K timed steps, and nothing after them (a plain run; with --full, under
+--no-cpu --no-clock), so its timed window is the LAST K dispatches of the resident kernel.  rocprofv3 --stats averages all dispatches, including the host-path pieces and the
 launches while the GPU clock ramps; this prints the average over the window bench.py's HIP events time.
 """
 import argparse
