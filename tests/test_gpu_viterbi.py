@@ -469,8 +469,9 @@ TEAM_VARIANTS = [v for v in msv.Viterbi_HMM.variants() if v.startswith("vit_w")]
 def test_team_variant_stress(name):
     """The team kernels (vit_team.hip: one sequence over W waves, LDS exchange per row) on the cases that
     exercise the exchange: the lazy-F stress model (D chains crossing many lanes AND the waves' boundaries),
-    distinct exit scores (per-lane C partials reduced across the team), and a batch mixing empty, 1-residue,
-    bad-length and long sequences -- bitwise against the oracle's DP over the same tables."""
+    distinct exit scores (per-lane C partials reduced across the team), on a batch of two empty sequences and 36
+    of length 1..700 (one per team: sequences refused for their length, and teams that score several sequences in
+    a row, are in test_gpu_queue_depth.py) -- bitwise against the oracle's DP over the same tables."""
     import re
     from hmm_fasta_viterbi_amd import _native
     m = re.match(r"vit_w(\d+)_s(\d+)_", name)
