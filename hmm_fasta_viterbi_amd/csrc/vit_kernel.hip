@@ -51,8 +51,11 @@ constexpr int kEarlyHopStates = 8;
 
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
 __device__ __forceinline__ uint64_t u64first(uint64_t x) {
-    return (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32))) << 32) |
-           __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x));
+    // (the builtin returns int: each half goes back to uint32_t before it is widened, or a low word with bit 31
+    // set -- a residue offset in [2^31, 2^32) -- would sign-extend over the high word)
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32)));
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)));
+    return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
 // Lane l-1's value into lane l (64 lanes); lane 0 keeps `old`'s lane 0, which its caller keeps at -inf

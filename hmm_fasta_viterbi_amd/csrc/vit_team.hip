@@ -87,8 +87,11 @@ __device__ __forceinline__ void lds_write4(float4* p, v4f v) { *(volatile LDS_AS
 __device__ __forceinline__ void lds_write2(float2* p, v2f v) { *(volatile LDS_AS v2f*)(p) = v; }
 __device__ __forceinline__ uint32_t ufirst(float x) { return __builtin_amdgcn_readfirstlane(__float_as_uint(x)); }
 __device__ __forceinline__ uint64_t u64first(uint64_t x) {
-    return (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32))) << 32) |
-           __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x));
+    // (the builtin returns int: each half goes back to uint32_t before it is widened, or a low word with bit 31
+    // set -- a residue offset in [2^31, 2^32) -- would sign-extend over the high word)
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32)));
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)));
+    return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
 }  // namespace

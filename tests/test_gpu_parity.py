@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 import hmm_fasta_viterbi_amd as msv
 from hmm_fasta_viterbi_amd.synthetic import concat_batches, homolog_batch, random_batch
 from oracle_lib import GOLD, PROFILES, ROOT, OracleProfile, bits, profile_path, read_golden_tsv
+from state_batches import numpy_msv as _numpy_msv
 
 _engines = {}
 
@@ -860,34 +861,6 @@ def test_homolog_sequences_match_oracle(prof):
     assert np.array_equal(bits(got), bits(want))
     small = e.score_batch(codes=hc[: int(ho[8])], offsets=ho[:9])  # latency-plan sized batch
     assert np.array_equal(bits(small), bits(want[:8]))
-
-
-def _numpy_msv(es, tBMk, tEC, tEJ, codes, offsets):
-    """float32 restatement of MSV_HMM::run_on_sequence (MSV_HMM.cpp:74-113) with free tr_E_C /
-    tr_E_J (the reference fixes both to logf(0.5f)); every add is one IEEE float32 op in the
-    reference's order, max is exact, so results are bit-comparable."""
-    f = np.float32
-    out = np.zeros(len(offsets) - 1, np.float32)
-    for s in range(len(offsets) - 1):
-        seq = codes[int(offsets[s]):int(offsets[s + 1])]
-        L = len(seq)
-        loop, move = msv.sequence_transitions(L)
-        loop, move = f(loop), f(move)
-        M = np.full(es.shape[1], -np.inf, np.float32)
-        J = C = f(-np.inf)
-        N, B = f(0.0), move
-        for r in seq:
-            Bt = f(B + f(tBMk))
-            newM = np.full_like(M, -np.inf)
-            newM[1:] = es[r, 1:] + np.maximum(M[:-1], Bt)
-            M = newM
-            E = M[1:].max()
-            J = max(f(J + loop), f(E + f(tEJ)))
-            C = max(f(C + loop), f(E + f(tEC)))
-            N = f(N + loop)
-            B = f(max(N, J) + move)
-        out[s] = f(C + move) if L else -np.inf
-    return out
 
 
 def test_distinct_tr_E_C_and_tr_E_J():
