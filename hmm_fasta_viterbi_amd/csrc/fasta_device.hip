@@ -34,6 +34,7 @@
 #include <cstring>
 #include <vector>
 
+#include "hip_rt.h"
 #include "msv.h"
 
 namespace fadev {
@@ -493,57 +494,24 @@ struct msv_fasta_device {
     int device = 0;
     uint64_t count = 0, rejected = 0, residues = 0, max_length = 0;
     uint8_t* d_codes = nullptr;   // final residue stream (either d_stage or d_final)
-    uint8_t* d_stage = nullptr;   // residues at their rank (incl. rejected records)
-    uint8_t* d_final = nullptr;   // compacted stream (only when a record was rejected)
-    uint64_t* d_offsets = nullptr;
-    uint64_t* d_spans = nullptr;
-    uint8_t* d_text = nullptr;    // owned copy of the text (msv_fasta_read_device only)
+    msvrt::DeviceBuffer<uint8_t> d_stage;  // residues at their rank (incl. rejected records)
+    msvrt::DeviceBuffer<uint8_t> d_final;  // compacted stream (only when a record was rejected)
+    msvrt::DeviceBuffer<uint64_t> d_offsets;
+    msvrt::DeviceBuffer<uint64_t> d_spans;
+    msvrt::DeviceBuffer<uint8_t> d_text;   // owned copy of the text (msv_fasta_read_device only)
 };
 
 namespace {
 
-struct Dev {
-    int prev = -1;
-    bool ok = false;
-    explicit Dev(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(d) == hipSuccess;
-    }
-    ~Dev() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+using msvrt::DeviceGuard;
 
-msv_status hip_status(hipError_t e) {
-    return e == hipErrorOutOfMemory ? MSV_ERR_OUT_OF_MEMORY : MSV_ERR_HIP;
-}
-
-#define FA_HIP(call)                               \
-    do {                                           \
-        hipError_t e_ = (call);                    \
-        if (e_ != hipSuccess) return hip_status(e_); \
-    } while (0)
-
-template <typename T>
-hipError_t dalloc(T*& p, uint64_t count) {
-    return hipMalloc(reinterpret_cast<void**>(&p), std::max<uint64_t>(count, 1) * sizeof(T));
-}
-
+// parse_on_device's scratch, freed when it returns
 struct Scratch {
-    uint2 *hs_ls = nullptr, *hs_ls_ex = nullptr, *pre_res = nullptr, *res = nullptr, *res_ex = nullptr;
-    uint2 *rv = nullptr, *rv_ex = nullptr, *part = nullptr;
-    fadev::TileCarry* carry = nullptr;
-    fadev::Totals* tot = nullptr;
-    uint32_t *rec_start = nullptr, *hdr_start = nullptr, *hdr_end = nullptr, *src = nullptr;
-    uint8_t* bad = nullptr;
-    ~Scratch() {
-        for (void* p : {static_cast<void*>(hs_ls), static_cast<void*>(hs_ls_ex), static_cast<void*>(pre_res),
-                        static_cast<void*>(res), static_cast<void*>(res_ex), static_cast<void*>(rv),
-                        static_cast<void*>(rv_ex), static_cast<void*>(part), static_cast<void*>(carry),
-                        static_cast<void*>(tot), static_cast<void*>(rec_start), static_cast<void*>(hdr_start),
-                        static_cast<void*>(hdr_end), static_cast<void*>(src), static_cast<void*>(bad)})
-            (void)hipFree(p);
-    }
+    msvrt::DeviceBuffer<uint2> hs_ls, hs_ls_ex, pre_res, res, res_ex, rv, rv_ex, part;
+    msvrt::DeviceBuffer<fadev::TileCarry> carry;
+    msvrt::DeviceBuffer<fadev::Totals> tot;
+    msvrt::DeviceBuffer<uint32_t> rec_start, hdr_start, hdr_end, src;
+    msvrt::DeviceBuffer<uint8_t> bad;
 };
 
 // Exclusive scan of n uint2 (3 launches); `part` holds >= ceil(n / 4096) elements.
@@ -565,64 +533,60 @@ msv_status parse_on_device(msv_fasta_device* f, const uint8_t* d_text, uint64_t 
     const uint32_t nt = std::max<uint32_t>(1, (N + kTileBytes - 1) / kTileBytes);
     const uint32_t tb = (nt + kThreads - 1) / kThreads;
     Scratch s;
-    FA_HIP(dalloc(s.hs_ls, nt));
-    FA_HIP(dalloc(s.hs_ls_ex, nt));
-    FA_HIP(dalloc(s.pre_res, nt));
-    FA_HIP(dalloc(s.res, nt));
-    FA_HIP(dalloc(s.res_ex, nt));
-    FA_HIP(dalloc(s.carry, nt));
-    FA_HIP(dalloc(s.part, (nt + kTile - 1) / kTile));
-    FA_HIP(dalloc(s.tot, 1));
-    FA_HIP(hipMemsetAsync(s.tot, 0, sizeof(Totals), st));
+    MSV_HIP(s.hs_ls.reserve(nt));
+    MSV_HIP(s.hs_ls_ex.reserve(nt));
+    MSV_HIP(s.pre_res.reserve(nt));
+    MSV_HIP(s.res.reserve(nt));
+    MSV_HIP(s.res_ex.reserve(nt));
+    MSV_HIP(s.carry.reserve(nt));
+    MSV_HIP(s.part.reserve((nt + kTile - 1) / kTile));
+    MSV_HIP(s.tot.reserve(1));
+    MSV_HIP(hipMemsetAsync(s.tot, 0, sizeof(Totals), st));
     hipLaunchKernelGGL(fa_tile_summary, dim3(nt), dim3(kThreads), 0, st, d_text, N, s.hs_ls, s.pre_res);
-    FA_HIP(hipGetLastError());
-    FA_HIP((scan_exclusive<0, 1>(s.hs_ls, nt, s.hs_ls_ex, s.part, st)));
+    MSV_HIP(hipGetLastError());
+    MSV_HIP((scan_exclusive<0, 1>(s.hs_ls, nt, s.hs_ls_ex, s.part, st)));
     hipLaunchKernelGGL(fa_tile_carry, dim3(tb), dim3(kThreads), 0, st, d_text, nt, s.hs_ls_ex, s.pre_res, s.res,
                        s.carry);
-    FA_HIP(hipGetLastError());
-    FA_HIP((scan_exclusive<0, 0>(s.res, nt, s.res_ex, s.part, st)));
+    MSV_HIP(hipGetLastError());
+    MSV_HIP((scan_exclusive<0, 0>(s.res, nt, s.res_ex, s.part, st)));
     hipLaunchKernelGGL(fa_tile_rexcl, dim3(tb), dim3(kThreads), 0, st, nt, s.res_ex, s.carry);
     hipLaunchKernelGGL(fa_tile_totals, dim3(1), dim3(1), 0, st, nt, s.hs_ls, s.hs_ls_ex, s.res, s.res_ex, s.tot);
-    FA_HIP(hipGetLastError());
+    MSV_HIP(hipGetLastError());
     Totals tot{};
-    FA_HIP(hipMemcpyAsync(&tot, s.tot, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    FA_HIP(hipStreamSynchronize(st));
+    MSV_HIP(hipMemcpyAsync(&tot, s.tot, sizeof(Totals), hipMemcpyDeviceToHost, st));
+    MSV_HIP(hipStreamSynchronize(st));
     const uint32_t nrec = tot.headers, R = tot.residues;
-    FA_HIP(dalloc(f->d_stage, R));
-    FA_HIP(dalloc(s.rec_start, nrec));
-    FA_HIP(dalloc(s.hdr_start, nrec));
-    FA_HIP(dalloc(s.hdr_end, nrec));
-    FA_HIP(dalloc(s.src, nrec));
-    FA_HIP(dalloc(s.bad, nrec));
-    FA_HIP(dalloc(s.rv, nrec));
-    FA_HIP(dalloc(s.rv_ex, nrec));
-    if ((nrec + kTile - 1) / kTile > (nt + kTile - 1) / kTile) {
-        (void)hipFree(s.part);
-        s.part = nullptr;
-        FA_HIP(dalloc(s.part, (nrec + kTile - 1) / kTile));
-    }
-    FA_HIP(dalloc(f->d_offsets, static_cast<uint64_t>(nrec) + 1));
-    FA_HIP(dalloc(f->d_spans, 2ull * nrec));
-    FA_HIP(hipMemsetAsync(f->d_offsets, 0, sizeof(uint64_t), st));  // nrec == 0: offsets = {0}
-    FA_HIP(hipMemsetAsync(s.hdr_end, 0xFF, std::max<uint32_t>(nrec, 1) * sizeof(uint32_t), st));
-    FA_HIP(hipMemsetAsync(s.bad, 0, std::max<uint32_t>(nrec, 1), st));
+    MSV_HIP(f->d_stage.reserve(R));
+    MSV_HIP(s.rec_start.reserve(nrec));
+    MSV_HIP(s.hdr_start.reserve(nrec));
+    MSV_HIP(s.hdr_end.reserve(nrec));
+    MSV_HIP(s.src.reserve(nrec));
+    MSV_HIP(s.bad.reserve(nrec));
+    MSV_HIP(s.rv.reserve(nrec));
+    MSV_HIP(s.rv_ex.reserve(nrec));
+    MSV_HIP(s.part.reserve((nrec + kTile - 1) / kTile));  // (grown only when the records need more tiles)
+    MSV_HIP(f->d_offsets.reserve(static_cast<uint64_t>(nrec) + 1));
+    MSV_HIP(f->d_spans.reserve(2ull * nrec));
+    MSV_HIP(hipMemsetAsync(f->d_offsets, 0, sizeof(uint64_t), st));  // nrec == 0: offsets = {0}
+    MSV_HIP(hipMemsetAsync(s.hdr_end, 0xFF, std::max<uint32_t>(nrec, 1) * sizeof(uint32_t), st));
+    MSV_HIP(hipMemsetAsync(s.bad, 0, std::max<uint32_t>(nrec, 1), st));
     hipLaunchKernelGGL(fa_tile_emit, dim3(nt), dim3(kThreads), 0, st, d_text, N, s.carry, f->d_stage, s.rec_start,
                        s.hdr_start, s.hdr_end, s.bad, s.tot);
-    FA_HIP(hipGetLastError());
+    MSV_HIP(hipGetLastError());
     if (nrec) {
         const uint32_t rb = (nrec + kThreads - 1) / kThreads;
         hipLaunchKernelGGL(fa_rec_values, dim3(rb), dim3(kThreads), 0, st, nrec, s.rec_start, s.bad, s.tot, s.rv);
-        FA_HIP(hipGetLastError());
+        MSV_HIP(hipGetLastError());
         const uint32_t npr = (nrec + kTile - 1) / kTile;
         hipLaunchKernelGGL((scan_reduce<1, 1>), dim3(npr), dim3(kThreads), 0, st, s.rv, nrec, s.part);
         hipLaunchKernelGGL(fa_max_partials, dim3(1), dim3(kScanThreads), 0, st, s.part, npr, s.tot);
-        FA_HIP((scan_exclusive<0, 0>(s.rv, nrec, s.rv_ex, s.part, st)));
+        MSV_HIP((scan_exclusive<0, 0>(s.rv, nrec, s.rv_ex, s.part, st)));
         hipLaunchKernelGGL(fa_rec_write, dim3(rb), dim3(kThreads), 0, st, nrec, N, s.rv, s.rv_ex, s.rec_start,
                            s.hdr_start, s.hdr_end, f->d_offsets, f->d_spans, s.src, s.tot);
-        FA_HIP(hipGetLastError());
+        MSV_HIP(hipGetLastError());
     }
-    FA_HIP(hipMemcpyAsync(&tot, s.tot, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    FA_HIP(hipStreamSynchronize(st));
+    MSV_HIP(hipMemcpyAsync(&tot, s.tot, sizeof(Totals), hipMemcpyDeviceToHost, st));
+    MSV_HIP(hipStreamSynchronize(st));
     if (tot.error & 1u) return MSV_ERR_PARSE;
     f->count = tot.kept;
     f->rejected = nrec - tot.kept;
@@ -630,12 +594,12 @@ msv_status parse_on_device(msv_fasta_device* f, const uint8_t* d_text, uint64_t 
     f->max_length = tot.max_len;
     f->d_codes = f->d_stage;
     if (f->rejected) {
-        FA_HIP(dalloc(f->d_final, tot.kept_res));
+        MSV_HIP(f->d_final.reserve(tot.kept_res));
         const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(4096, (tot.kept + 3) / 4));
         hipLaunchKernelGGL(fa_compact, dim3(blocks), dim3(kThreads), 0, st, f->d_stage, tot.kept, f->d_offsets,
                            s.src, f->d_final);
-        FA_HIP(hipGetLastError());
-        FA_HIP(hipStreamSynchronize(st));
+        MSV_HIP(hipGetLastError());
+        MSV_HIP(hipStreamSynchronize(st));
         f->d_codes = f->d_final;
     }
     return MSV_OK;
@@ -647,12 +611,7 @@ extern "C" {
 
 void msv_fasta_device_destroy(msv_fasta_device* f) {
     if (!f) return;
-    Dev g(f->device);
-    (void)hipFree(f->d_stage);
-    (void)hipFree(f->d_final);
-    (void)hipFree(f->d_offsets);
-    (void)hipFree(f->d_spans);
-    (void)hipFree(f->d_text);
+    DeviceGuard g(f->device);
     delete f;
 }
 
@@ -660,7 +619,7 @@ msv_status msv_fasta_parse_device(int device, const uint8_t* d_text, uint64_t n,
                                   msv_fasta_device** out) {
     if (!out || (n && !d_text)) return MSV_ERR_INVALID_ARGUMENT;
     *out = nullptr;
-    Dev g(device);
+    DeviceGuard g(device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     auto* f = new (std::nothrow) msv_fasta_device();
     if (!f) return MSV_ERR_OUT_OF_MEMORY;
@@ -677,7 +636,7 @@ msv_status msv_fasta_parse_device(int device, const uint8_t* d_text, uint64_t n,
 msv_status msv_fasta_read_device(int device, const char* path, void* stream, msv_fasta_device** out) {
     if (!path || !out) return MSV_ERR_INVALID_ARGUMENT;
     *out = nullptr;
-    Dev g(device);
+    DeviceGuard g(device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     std::FILE* fp = std::fopen(path, "rb");
     if (!fp) return MSV_ERR_IO;
@@ -702,14 +661,13 @@ msv_status msv_fasta_read_device(int device, const char* path, void* stream, msv
     f->device = device;
     // pinned staging in 64 MiB pieces: file read of piece k+1 overlaps the H2D copy of piece k
     constexpr uint64_t kPiece = 64ull << 20;
-    uint8_t* pinned[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
+    msvrt::PinnedBuffer<uint8_t> pinned[2];
+    msvrt::Event done[2];
     msv_status s = MSV_OK;
-    if (dalloc(f->d_text, n) != hipSuccess) s = MSV_ERR_OUT_OF_MEMORY;
+    if (f->d_text.reserve(n) != hipSuccess) s = MSV_ERR_OUT_OF_MEMORY;
     for (int k = 0; k < 2 && s == MSV_OK; ++k) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&pinned[k]), std::min(kPiece, std::max<uint64_t>(n, 1))) !=
-                hipSuccess ||
-            hipEventCreateWithFlags(&done[k], hipEventDisableTiming) != hipSuccess)
+        if (pinned[k].reserve(std::min(kPiece, std::max<uint64_t>(n, 1)), hipHostMallocDefault) != hipSuccess ||
+            done[k].create(hipEventDisableTiming) != hipSuccess)
             s = MSV_ERR_OUT_OF_MEMORY;
     }
     for (uint64_t off = 0, k = 0; s == MSV_OK && off < n; off += kPiece, ++k) {
@@ -723,9 +681,9 @@ msv_status msv_fasta_read_device(int device, const char* path, void* stream, msv
     }
     std::fclose(fp);
     if (s == MSV_OK && hipStreamSynchronize(st) != hipSuccess) s = MSV_ERR_HIP;
-    for (int k = 0; k < 2; ++k) {
-        if (pinned[k]) (void)hipHostFree(pinned[k]);
-        if (done[k]) (void)hipEventDestroy(done[k]);
+    for (int k = 0; k < 2; ++k) {  // the staging goes before the parse allocates its scratch
+        pinned[k].reset();
+        done[k].reset();
     }
     if (s == MSV_OK) s = parse_on_device(f, f->d_text, n, st);
     if (s != MSV_OK) {
@@ -738,11 +696,11 @@ msv_status msv_fasta_read_device(int device, const char* path, void* stream, msv
 
 msv_status msv_fasta_device_download(const msv_fasta_device* f, uint8_t* codes, uint64_t* offsets, uint64_t* spans) {
     if (!f) return MSV_ERR_INVALID_ARGUMENT;
-    Dev g(f->device);
+    DeviceGuard g(f->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    if (codes && f->residues) FA_HIP(hipMemcpy(codes, f->d_codes, f->residues, hipMemcpyDeviceToHost));
-    if (offsets) FA_HIP(hipMemcpy(offsets, f->d_offsets, (f->count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (spans && f->count) FA_HIP(hipMemcpy(spans, f->d_spans, 2 * f->count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (codes && f->residues) MSV_HIP(hipMemcpy(codes, f->d_codes, f->residues, hipMemcpyDeviceToHost));
+    if (offsets) MSV_HIP(hipMemcpy(offsets, f->d_offsets, (f->count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (spans && f->count) MSV_HIP(hipMemcpy(spans, f->d_spans, 2 * f->count * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return MSV_OK;
 }
 

@@ -17,4 +17,18 @@ float run_on_sequence(const float* emission_scores, size_t M, float tr_B_Mk, flo
 float viterbi_run_on_sequence(const float* msc, const float* isc, const float* tsc, size_t M, float tr_B_Mk,
                               float tr_E_C, float tr_E_J, const uint8_t* codes, size_t L);
 
+// Kernel-layout tables (table_layout.cpp, where the layouts are written out), from the [20][model_length]
+// residue-major host tables.  The device layer uploads them as they are.
+// An MSV variant of G lanes per sequence, S states per lane, the first sa of them in LDS (0: the whole row).
+std::vector<float> msv_variant_table(const float* es, uint32_t model_length, int G, int S, int sa);
+// A cooperative MSV variant of `waves` waves of 64 lanes x S states, neighbours sharing `halo` states.
+std::vector<float> msv_coop_table(const float* es, uint32_t model_length, int waves, int S, int sa, int halo);
+// A Viterbi variant of S states per lane and `team` waves per sequence: match, insert (empty unless isc)
+// and transition tables, each a sequence of float pairs (the kernels' float2).
+struct VitTables {
+    std::vector<float> et, it, tt;
+};
+VitTables vit_tables(const float* msc, const float* isc_tab, const float* tsc, uint32_t model_length, int S, int team,
+                     bool isc);
+
 }  // namespace msv_host

@@ -16,11 +16,13 @@
 
 #include <cstdint>
 
+#include "hip_rt.h"
+
 namespace msvrt {
 
 template <int N>
 struct LaunchRing {
-    hipEvent_t done[N] = {};
+    Event done[N];
     hipStream_t last[N] = {};  // nullptr: never launched
     bool recorded[N] = {};     // done[k] covers the slot's last launch
     bool dirty[N] = {};        // a launch failed after the slot's counters were touched
@@ -29,12 +31,11 @@ struct LaunchRing {
     // Creates every slot's event up front (created lazily, the first N launches of a fresh profile
     // would each pay an event creation).
     hipError_t create_events() {
-        for (hipEvent_t& e : done)
-            if (!e) {
-                // device-scope release: the event only orders this device's streams
-                const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToDevice);
-                if (r != hipSuccess) return r;
-            }
+        for (Event& e : done) {
+            // device-scope release: the event only orders this device's streams
+            const hipError_t r = e.create(hipEventDisableTiming | hipEventReleaseToDevice);
+            if (r != hipSuccess) return r;
+        }
         return hipSuccess;
     }
 
@@ -42,10 +43,8 @@ struct LaunchRing {
     // that ran on another stream.
     hipError_t acquire(hipStream_t st, int* slot) {
         const int k = static_cast<int>(next++ % N);
-        if (!done[k]) {
-            const hipError_t e = hipEventCreateWithFlags(&done[k], hipEventDisableTiming | hipEventReleaseToDevice);
-            if (e != hipSuccess) return e;
-        }
+        const hipError_t made = done[k].create(hipEventDisableTiming | hipEventReleaseToDevice);
+        if (made != hipSuccess) return made;
         if (last[k] && last[k] != st) {
             // Nothing to wait for when the slot's last launch has completed: its stream is idle, or its
             // recorded event has fired (host queries, no packets -- a fused grid call acquires a slot
@@ -81,10 +80,6 @@ struct LaunchRing {
                 recorded[k] = true;
             }
         return hipSuccess;
-    }
-    void destroy() {
-        for (hipEvent_t& e : done)
-            if (e) (void)hipEventDestroy(e);
     }
 };
 

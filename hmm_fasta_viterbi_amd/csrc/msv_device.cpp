@@ -19,9 +19,23 @@
 #include <thread>
 #include <vector>
 
+#include "hip_rt.h"
+#include "host_cpu.h"
 #include "launch_ring.h"
 #include "msv.h"
 #include "msv_kernel.h"
+
+using msvrt::csr_extent;
+using msvrt::DeviceBuffer;
+using msvrt::DeviceGuard;
+using msvrt::hip_status;
+using msvrt::kChunkBytes;
+using msvrt::kMaxLaunchSeqs;
+using msvrt::mapped_host;
+using msvrt::PinnedBuffer;
+
+// table_layout.cpp builds the tables without msv_kernel.h
+static_assert(msvk::kAminoAcids == 20 && msvk::kPoisonRow == 20 && msvk::kTableRows == 21, "table_layout.cpp's rows");
 
 namespace {
 
@@ -39,8 +53,6 @@ constexpr int kAsyncSlots = 3;
 constexpr int kErrWord = 2 * kLaunchSlots;
 constexpr int kHostErrWord = kErrWord + 1 + kAsyncSlots;
 constexpr int kWords = kHostErrWord + 1;
-// Every launch addresses < 2^32 residue bytes.
-constexpr uint64_t kChunkBytes = (1ull << 32) - (1ull << 20);
 // Host batches of at least this many residues are scored as a copy/compute pipeline of pieces.
 constexpr uint64_t kPipelineMin = 4ull << 20;
 // Small host calls (pageable residues of at most kSmallCall bytes, at most kSmallCall sequences -- the
@@ -51,18 +63,6 @@ constexpr uint64_t kSmallCall = 1ull << 20;
 // batch at least kInPlaceAnyBytes residues (msv_score_batch).
 constexpr uint32_t kInPlaceMinStates = 300;
 constexpr uint64_t kInPlaceAnyBytes = 16ull << 20;
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 // MSV_HMM::init_transitions_depend_on_seq (MSV_HMM.cpp:59-64) for every length < n, with the
 // host's logf (never a device logf, so the per-sequence constants are the reference's bits).
@@ -83,31 +83,6 @@ std::vector<float2> host_length_table(uint32_t n) {
     }
     return std::vector<float2>(table.begin(), table.begin() + n);
 }
-
-template <typename T>
-hipError_t ensure(T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t n = std::max<size_t>(need, 1);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-}
-
-msv_status hip_status(hipError_t e) {
-    if (e == hipSuccess) return MSV_OK;
-    if (e == hipErrorOutOfMemory) return MSV_ERR_OUT_OF_MEMORY;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return MSV_ERR_NO_DEVICE;
-    return MSV_ERR_HIP;
-}
-
-#define MSV_HIP(call)                                    \
-    do {                                                 \
-        hipError_t e_ = (call);                          \
-        if (e_ != hipSuccess) return hip_status(e_);     \
-    } while (0)
 
 // Estimated issue cost of one row for one sequence: 2.5 VALU per state-slot plus the per-row
 // specials/reduction, times the lanes a sequence occupies.  A BIG table costs little with one
@@ -192,7 +167,7 @@ using LaunchRing = msvrt::LaunchRing<kLaunchSlots>;
 struct Plan {
     const msvk::Variant* v = nullptr;
     const msvk::CoopVariant* cv = nullptr;  // the cooperative plan (msv_coop.hip) instead of a variant
-    float4* d_etab = nullptr;
+    DeviceBuffer<float4> d_etab;
     int blocks = 0;  // persistent grid size
     int groups_per_block = 0;
 };
@@ -212,24 +187,22 @@ struct msv_profile {
     uint64_t mid_max_n = 0;       // batches above lat_max_n and up to this many take the mid plan
     float tr_B_Mk = 0, tr_E_C = 0, tr_E_J = 0;
     std::vector<float> emission_scores;  // host copy [20][model_length] (for re-layout)
-    float2* d_lentab = nullptr;
+    DeviceBuffer<float2> d_lentab;
     uint32_t lentab_n = 0;
-    uint32_t* d_words = nullptr;  // kLaunchSlots x {dequeue counter, waves still running}, sticky error bits
-    uint32_t* d_hist = nullptr;   // kLaunchSlots longest-first counting-sort scratches [hist | cursors]
+    DeviceBuffer<uint32_t> d_words;  // kLaunchSlots x {dequeue counter, waves still running}, sticky error bits
+    DeviceBuffer<uint32_t> d_hist;  // kLaunchSlots longest-first counting-sort scratches [hist | cursors]
     std::array<bool, kLaunchSlots> hist_dirty{};  // histogram not known to be zero (fresh, failed launch)
-    uint8_t* d_dummy = nullptr;   // a readable residue byte for batches with no residues
+    DeviceBuffer<uint8_t> d_dummy;  // a readable residue byte for batches with no residues
     LaunchRing kernels, orders;   // launch slots of the MSV kernel and of the order sort
-    hipStream_t stream = nullptr;
+    msvrt::Stream stream;
     hipStream_t bound = nullptr;  // msv_profile_bind_stream: a caller stream guaranteed alive while bound
     // host-API pipeline (msv_score_batch): a second compute stream, a copy stream, piece events,
     // and pinned staging for the rebased offsets
-    hipStream_t stream2 = nullptr, copy_stream = nullptr;
-    hipStream_t offsets_stream = nullptr;  // msv_score_batch_async: the offsets' H2D, beside the residues'
-    std::vector<hipEvent_t> events;
-    uint64_t* h_off = nullptr;
-    size_t h_off_cap = 0;
-    float* h_sc = nullptr;  // pinned score staging of small calls with pageable destinations
-    size_t h_sc_cap = 0;
+    msvrt::Stream stream2, copy_stream;
+    msvrt::Stream offsets_stream;  // msv_score_batch_async: the offsets' H2D, beside the residues'
+    std::vector<msvrt::Event> events;
+    PinnedBuffer<uint64_t> h_off;
+    PinnedBuffer<float> h_sc;  // pinned score staging of small calls with pageable destinations
     uint32_t pipe_first_den = 4, pipe_growth = 2;  // piece sizes: total / first_den, then x growth
     uint32_t pipe_streams = 2;                      // compute streams the pieces alternate over
     bool zero_copy = true;  // page-locked residues read in place (msv_debug_set_zero_copy turns it off)
@@ -237,37 +210,28 @@ struct msv_profile {
     // msv_score_batch_async: kAsyncSlots staging sets, so the H2D of one call runs under the kernel
     // of the call before it
     struct AsyncSlot {
-        uint8_t* d_res = nullptr;
-        size_t res_cap = 0;
-        uint64_t* d_off = nullptr;
-        size_t off_cap = 0;
-        float* d_sc = nullptr;
-        size_t sc_cap = 0;
-        uint32_t* d_ord = nullptr;
-        size_t ord_cap = 0;
-        uint64_t* h_off = nullptr;  // pinned rebased offsets
-        size_t h_cap = 0;
-        uint32_t* h_err = nullptr;  // pinned copy of the slot's error word
+        DeviceBuffer<uint8_t> d_res;
+        DeviceBuffer<uint64_t> d_off;
+        DeviceBuffer<float> d_sc;
+        DeviceBuffer<uint32_t> d_ord;
+        PinnedBuffer<uint64_t> h_off;  // pinned rebased offsets
+        PinnedBuffer<uint32_t> h_err;  // pinned copy of the slot's error word
         const float* direct = nullptr;  // page-locked destination written by the kernel (errors: scan)
         uint64_t n = 0;
-        hipEvent_t copied = nullptr, done = nullptr, off_copied = nullptr;
+        msvrt::Event copied, done, off_copied;
         uint64_t ticket = 0;
         bool pending = false;
     } async[kAsyncSlots];
     uint64_t next_ticket = 1;
     // host-API staging
-    uint8_t* d_res = nullptr;
-    size_t d_res_cap = 0;
-    uint64_t* d_off = nullptr;
-    size_t d_off_cap = 0;
-    float* d_scores = nullptr;
-    size_t d_scores_cap = 0;
-    uint32_t* d_order = nullptr;  // msv_score_fasta_device's longest-first order
-    size_t d_order_cap = 0;
+    DeviceBuffer<uint8_t> d_res;
+    DeviceBuffer<uint64_t> d_off;
+    DeviceBuffer<float> d_scores;
+    DeviceBuffer<uint32_t> d_order;  // msv_score_fasta_device's longest-first order
     uint64_t* d_stamps = nullptr;  // diagnostic timeline buffer (tools only), or nullptr
     bool stamp_clock = false;      // d_stamps is for the CLOCK twins (kStampWords per wave: bench.py clock_GHz)
     hipEvent_t time_start = nullptr, time_stop = nullptr;  // msv_debug_time_next_launch (one launch)
-    hipEvent_t done = nullptr;     // grid API: joins this profile's stream back to the caller's
+    msvrt::Event done;             // grid API: joins this profile's stream back to the caller's
     hipStream_t shared = nullptr;  // shared_stream(device) once a host grid call used it
 };
 
@@ -294,30 +258,6 @@ static bool lazy_stream(const msv_profile* p, hipStream_t st) {
     return st == p->stream || st == p->stream2 || (p->bound && st == p->bound) || (p->shared && st == p->shared);
 }
 
-// Device address of a page-locked host destination the kernels can write directly (nullptr for
-// pageable memory).  Host paths then need no score D2H: the kernels' stores cross PCIe as they are
-// made (a few MB of posted writes spread over the launch), and the end-of-kernel system-scope
-// release makes them visible before the completion the host waits on.  (A staged D2H of the scores
-// was dispatched as a blit KERNEL when queued behind the next call's launch, and starved there: the
-// persistent MSV grid holds every CU -- profiles/r02_host_pipeline_timeline.txt.)
-// (The same alias lets a kernel READ page-locked residues in place: see msv_score_batch.)
-template <typename T>
-static T* mapped_host(T* host) {
-    hipPointerAttribute_t at{};
-    void* h = const_cast<void*>(static_cast<const void*>(host));
-    if (hipPointerGetAttributes(&at, h) != hipSuccess) {
-        (void)hipGetLastError();  // pageable memory is not an error here
-        return nullptr;
-    }
-    if (at.type != hipMemoryTypeHost) return nullptr;
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return static_cast<T*>(d);
-}
-
 // The status of a kernel's latched error bits (msv_kernel.h kErr*), most specific first.
 static msv_status err_status(uint32_t err) {
     if (err & msvk::kErrBadOrder) return MSV_ERR_INVALID_ARGUMENT;  // an order entry outside the batch
@@ -342,80 +282,26 @@ static msv_status scan_scores(const float* scores, uint64_t n) {
     return MSV_OK;
 }
 
-// Lays the MSV table out for variant v and uploads it:
-// [row r][chunk c][lane gl] float4 = e[r][gl*S + 4c + 1 .. +4]; states beyond LENG are -inf
-// (never win a max); row 20 is the +inf poison row for codes >= 20.
-// Split variants (v->sa > 0, G = 32/64, lane gl owns states gl*S + 1 .. gl*S + S as usual): an A table
-// [20 rows][SA/4][G] float4 (the lane's first SA states, staged in LDS) followed by a B table
-// [21 rows][G][HBP] float2 (its last S - SA states as HB = (S-SA)/2 halves padded to HBP = even,
-// lane-contiguous so a lane reads them as HBP/2 float4 loads from L2; row 20 = poison).
+// Lays the MSV table out for variant v (msv_host::msv_variant_table) and uploads it.
 static msv_status install_plan(msv_profile* p, const msvk::Variant* v, Plan& plan) {
-    const uint32_t model_length = p->model_length, R = model_length - 1;
-    const int G = v->G, S = v->S, C4 = S / 4;
-    const float ninf = -std::numeric_limits<float>::infinity();
-    const float pinf = std::numeric_limits<float>::infinity();
-    std::vector<float> tab;
-    // one [rows][chunks][G] block of `width`-float chunks whose lane gl, chunk c, slot q holds state
-    // first + gl*span + width*c + q
-    auto block = [&](int rows, int chunks, uint32_t first, int span, int width) {
-        for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < chunks; ++c)
-                for (int gl = 0; gl < G; ++gl)
-                    for (int q = 0; q < width; ++q) {
-                        const uint32_t j = first + static_cast<uint32_t>(gl * span + width * c + q);  // state 1..
-                        float val;
-                        if (r == msvk::kPoisonRow) val = pinf;
-                        else val = (j <= R) ? p->emission_scores[static_cast<size_t>(r) * model_length + j] : ninf;
-                        tab.push_back(val);
-                    }
-    };
-    if (v->sa > 0) {
-        block(msvk::kAminoAcids, v->sa / 4, 1, S, 4);
-        // B table [21 rows][G][HBP] float2, lane-contiguous (each lane reads HBP/2 float4), HBP = the
-        // lane's HB = (S - SA)/2 halves rounded up to even (the pad half is -inf and never read)
-        const int HB = (S - v->sa) / 2, HBP = (HB + 1) & ~1;
-        for (int r = 0; r < msvk::kTableRows; ++r)
-            for (int gl = 0; gl < G; ++gl)
-                for (int h = 0; h < HBP; ++h)
-                    for (int q = 0; q < 2; ++q) {
-                        const uint32_t j = static_cast<uint32_t>(v->sa + 1 + gl * S + 2 * h + q);  // state 1..
-                        float val;
-                        if (r == msvk::kPoisonRow) val = pinf;
-                        else if (h < HB && j <= R) val = p->emission_scores[static_cast<size_t>(r) * model_length + j];
-                        else val = ninf;
-                        tab.push_back(val);
-                    }
-    } else {
-        block(msvk::kTableRows, C4, 1, S, 4);
-    }
-    float4* d = nullptr;
-    MSV_HIP(hipMalloc(reinterpret_cast<void**>(&d), tab.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return hip_status(e);
-    }
-    if (plan.d_etab) {  // may be read by an in-flight launch on any stream the caller used
-        (void)hipDeviceSynchronize();
-        (void)hipFree(plan.d_etab);
-    }
-    plan.d_etab = d;
+    const std::vector<float> tab =
+        msv_host::msv_variant_table(p->emission_scores.data(), p->model_length, v->G, v->S, v->sa);
+    // (the old table may be read by an in-flight launch on any stream the caller used: replace_with)
+    MSV_HIP(plan.d_etab.replace_with(reinterpret_cast<const float4*>(tab.data()), tab.size() / 4));
     plan.v = v;
     hipDeviceProp_t prop;
     MSV_HIP(hipGetDeviceProperties(&prop, p->device));
     int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(v->fn), v->waves * 64, 0);
+    const hipError_t e =
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(v->fn), v->waves * 64, 0);
     if (e != hipSuccess || per_cu < 1) per_cu = 1;
     plan.blocks = prop.multiProcessorCount * per_cu;
-    plan.groups_per_block = v->waves * (64 / G) * v->streams;
+    plan.groups_per_block = v->waves * (64 / v->G) * v->streams;
     return MSV_OK;
 }
 
 static void drop_plan(Plan& plan) {
-    if (plan.d_etab) {  // may be read by an in-flight launch
-        (void)hipDeviceSynchronize();
-        (void)hipFree(plan.d_etab);
-    }
+    if (plan.d_etab) (void)hipDeviceSynchronize();  // may be read by an in-flight launch
     plan = Plan{};
 }
 
@@ -434,42 +320,14 @@ static const msvk::CoopVariant* pick_coop_variant(uint32_t states) {
     return cv;
 }
 
-// Lays p's table out for cooperative variant cv into `plan` (d_etab, cv).
+// Lays p's table out for cooperative variant cv (msv_host::msv_coop_table) into `plan` (d_etab, cv).
 static msv_status install_coop_table(msv_profile* p, const msvk::CoopVariant* cv, Plan& plan) {
-    const uint32_t R = p->model_length - 1;
-    // [21 rows][waves][SA/2 chunks][64 lanes] float2 (staged in LDS): wave w, lane l, chunk h, slot q holds
-    // global state w * (64 S - halo) - halo + l S + 2h + q + 1; split variants (SA < S) append
-    // [21 rows][waves][64 lanes][S - SA] floats for the lane's states SA .. S-1 (read from L2 per row).
-    // States outside 1..LENG are -inf; row 20 is the +inf poison row.
-    const int W = cv->waves, S = cv->S, SA = cv->sa, H = SA / 2, SB = S - SA;
-    const float ninf = -std::numeric_limits<float>::infinity();
-    const float pinf = std::numeric_limits<float>::infinity();
-    auto value = [&](int r, int w, int l, int k) {
-        const int64_t j = static_cast<int64_t>(w) * (64 * S - cv->halo) - cv->halo + l * S + k + 1;
-        if (r == msvk::kPoisonRow) return pinf;
-        return (j >= 1 && j <= R) ? p->emission_scores[static_cast<size_t>(r) * p->model_length + j] : ninf;
-    };
-    std::vector<float> tab;
-    tab.reserve(static_cast<size_t>(msvk::kTableRows) * W * 64 * S);
-    for (int r = 0; r < msvk::kTableRows; ++r)
-        for (int w = 0; w < W; ++w)
-            for (int h = 0; h < H; ++h)
-                for (int l = 0; l < 64; ++l)
-                    for (int q = 0; q < 2; ++q) tab.push_back(value(r, w, l, 2 * h + q));
-    for (int r = 0; r < msvk::kTableRows && SB > 0; ++r)
-        for (int w = 0; w < W; ++w)
-            for (int l = 0; l < 64; ++l)
-                for (int i = 0; i < SB; ++i) tab.push_back(value(r, w, l, SA + i));
-    float4* d = nullptr;
-    MSV_HIP(hipMalloc(reinterpret_cast<void**>(&d), tab.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return hip_status(e);
-    }
-    drop_plan(plan);
-    plan.d_etab = d;
+    const std::vector<float> tab =
+        msv_host::msv_coop_table(p->emission_scores.data(), p->model_length, cv->waves, cv->S, cv->sa, cv->halo);
+    MSV_HIP(plan.d_etab.replace_with(reinterpret_cast<const float4*>(tab.data()), tab.size() / 4));
+    plan.v = nullptr;
     plan.cv = cv;
+    plan.blocks = 0;
     plan.groups_per_block = 1;
     return MSV_OK;
 }
@@ -594,7 +452,7 @@ static msv_status install_variant(msv_profile* p, const msvk::Variant* main_v) {
 // of the batch (at least 1M residues) and grow `growth`-fold, a short remainder joining the last piece.
 static std::vector<uint64_t> plan_pieces(const uint64_t* offsets, uint64_t n, uint64_t total, uint32_t first_den,
                                          uint32_t growth) {
-    constexpr uint64_t kMaxSeqs = (1ull << 32) - (1ull << 24) - 1;
+    constexpr uint64_t kMaxSeqs = kMaxLaunchSeqs - 1;
     std::vector<uint64_t> cut{0};
     uint64_t want = (total < kPipelineMin || first_den == 0) ? kChunkBytes
                                                              : std::max<uint64_t>(1ull << 20, total / first_den);
@@ -635,43 +493,8 @@ void msv_profile_destroy(msv_profile* p) {
     if (!p) return;
     DeviceGuard g(p->device);
     // work still queued on any stream (an unwaited msv_score_batch_async call, a device call on the
-    // caller's stream) may use the buffers and pinned staging freed below
+    // caller's stream) may use the buffers and pinned staging that the members' destructors free
     (void)hipDeviceSynchronize();
-    (void)hipFree(p->main.d_etab);
-    (void)hipFree(p->lat.d_etab);
-    (void)hipFree(p->mid.d_etab);
-    (void)hipFree(p->fused.d_etab);
-    (void)hipFree(p->coop.d_etab);
-    (void)hipFree(p->coop_fused.d_etab);
-    (void)hipFree(p->d_lentab);
-    (void)hipFree(p->d_words);
-    (void)hipFree(p->d_hist);
-    (void)hipFree(p->d_dummy);
-    (void)hipFree(p->d_res);
-    (void)hipFree(p->d_off);
-    (void)hipFree(p->d_scores);
-    (void)hipFree(p->d_order);
-    if (p->h_off) (void)hipHostFree(p->h_off);
-    if (p->h_sc) (void)hipHostFree(p->h_sc);
-    if (p->done) (void)hipEventDestroy(p->done);
-    for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
-    p->kernels.destroy();
-    p->orders.destroy();
-    for (auto& a : p->async) {
-        if (a.copied) (void)hipEventDestroy(a.copied);
-        if (a.off_copied) (void)hipEventDestroy(a.off_copied);
-        if (a.done) (void)hipEventDestroy(a.done);
-        (void)hipFree(a.d_res);
-        (void)hipFree(a.d_off);
-        (void)hipFree(a.d_sc);
-        (void)hipFree(a.d_ord);
-        if (a.h_off) (void)hipHostFree(a.h_off);
-        if (a.h_err) (void)hipHostFree(a.h_err);
-    }
-    if (p->stream) (void)hipStreamDestroy(p->stream);
-    if (p->stream2) (void)hipStreamDestroy(p->stream2);
-    if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
-    if (p->offsets_stream) (void)hipStreamDestroy(p->offsets_stream);
     delete p;
 }
 
@@ -684,19 +507,8 @@ msv_status msv_profile_reserve_length(msv_profile* p, uint64_t max_length) {
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     const uint32_t n = std::max(need, p->lentab_n * 2);
     const std::vector<float2> host = host_length_table(n);
-    float2* d = nullptr;
-    MSV_HIP(hipMalloc(reinterpret_cast<void**>(&d), n * sizeof(float2)));
-    hipError_t e = hipMemcpy(d, host.data(), n * sizeof(float2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return hip_status(e);
-    }
-    // the old table may still be read by an in-flight launch on any stream the caller used
-    if (p->d_lentab) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(p->d_lentab);
-    }
-    p->d_lentab = d;
+    // (the old table may still be read by an in-flight launch on any stream the caller used: replace_with)
+    MSV_HIP(p->d_lentab.replace_with(host.data(), n));
     p->lentab_n = n;
     return MSV_OK;
 }
@@ -724,7 +536,7 @@ msv_status msv_profile_create(int device, const float* emission_scores, uint32_t
 
     p->emission_scores.assign(emission_scores, emission_scores + static_cast<size_t>(20) * model_length);
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking)) != hipSuccess) {
+    if ((e = p->stream.create(hipStreamNonBlocking)) != hipSuccess) {
         msv_profile_destroy(p);
         return hip_status(e);
     }
@@ -735,10 +547,9 @@ msv_status msv_profile_create(int device, const float* emission_scores, uint32_t
             msv_profile_destroy(p);
             return hip_status(e);
         }
-    if ((e = hipMalloc(reinterpret_cast<void**>(&p->d_words), kWords * sizeof(uint32_t))) != hipSuccess ||
+    if ((e = p->d_words.reserve(kWords)) != hipSuccess ||
         (e = hipMemset(p->d_words, 0, kWords * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&p->d_dummy), 64)) != hipSuccess ||
-        (e = hipMemset(p->d_dummy, 0, 64)) != hipSuccess) {
+        (e = p->d_dummy.reserve(64)) != hipSuccess || (e = hipMemset(p->d_dummy, 0, 64)) != hipSuccess) {
         msv_profile_destroy(p);
         return hip_status(e);
     }
@@ -927,7 +738,7 @@ static msv_status launch_batch(msv_profile* p, const uint8_t* d_residues, uint64
     if (!p) return MSV_ERR_INVALID_ARGUMENT;
     if (n == 0) return MSV_OK;
     if (!d_offsets || !d_scores || (residues_len && !d_residues)) return MSV_ERR_INVALID_ARGUMENT;
-    if (residues_len >= (1ull << 32) || n >= (1ull << 32) - (1ull << 24)) return MSV_ERR_INVALID_ARGUMENT;
+    if (residues_len >= (1ull << 32) || n >= kMaxLaunchSeqs) return MSV_ERR_INVALID_ARGUMENT;
     DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : p->stream;
@@ -1044,8 +855,7 @@ msv_status msv_order_longest_first(msv_profile* p, const uint64_t* d_offsets, ui
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : p->stream;
     if (!p->d_hist) {
-        MSV_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_hist),
-                            kLaunchSlots * msvk::kOrderScratchWords(kOrderBins) * sizeof(uint32_t)));
+        MSV_HIP(p->d_hist.reserve(kLaunchSlots * msvk::kOrderScratchWords(kOrderBins)));
         p->hist_dirty.fill(true);
     }
     int k = 0;
@@ -1078,15 +888,12 @@ msv_status msv_score_batch(msv_profile* p, const uint8_t* residues, const uint64
     if (!p || (n && (!offsets || !scores))) return MSV_ERR_INVALID_ARGUMENT;
     if (n == 0) return MSV_OK;
     // Validate the CSR on the host (cheap, O(n)) and find the longest sequence.
-    uint64_t maxL = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-        if (offsets[s + 1] < offsets[s]) return MSV_ERR_INVALID_ARGUMENT;
-        maxL = std::max<uint64_t>(maxL, offsets[s + 1] - offsets[s]);
-    }
+    uint64_t maxL = 0, total = 0;
+    msv_status s = csr_extent(offsets, n, &maxL, &total);
+    if (s != MSV_OK) return s;
     if (maxL >= kChunkBytes) return MSV_ERR_SEQUENCE_TOO_LONG;
-    const uint64_t total = offsets[n] - offsets[0];
     if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
-    msv_status s = msv_profile_reserve_length(p, maxL);
+    s = msv_profile_reserve_length(p, maxL);
     if (s != MSV_OK) return s;
 
     DeviceGuard g(p->device);
@@ -1122,60 +929,39 @@ msv_status msv_score_batch(msv_profile* p, const uint8_t* residues, const uint64
     // (profiles/r03_reference_call_timeline.txt).
     const bool small = !zres && total <= kSmallCall && n <= kSmallCall;
     const uint64_t res_words = small ? (total + 7) / 8 : 0;
-    if (!zres && !small) MSV_HIP(ensure(p->d_res, p->d_res_cap, std::max<uint64_t>(total, 1)));
-    MSV_HIP(ensure(p->d_off, p->d_off_cap, n + P + res_words));
+    if (!zres && !small) MSV_HIP(p->d_res.reserve(std::max<uint64_t>(total, 1)));
+    MSV_HIP(p->d_off.reserve(n + P + res_words));
     // a page-locked destination is written by the kernels themselves (no D2H of the scores)
     float* direct = mapped_host(scores);
     const bool staged_scores = !direct && small;
     if (staged_scores) {
-        if (p->h_sc_cap < n) {
-            if (p->h_sc) (void)hipHostFree(p->h_sc);
-            p->h_sc = nullptr;
-            p->h_sc_cap = 0;
-            MSV_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_sc), std::max<uint64_t>(n, 64) * sizeof(float),
-                                  hipHostMallocDefault));
-            p->h_sc_cap = std::max<uint64_t>(n, 64);
-        }
-        direct = mapped_host(p->h_sc);
+        MSV_HIP(p->h_sc.reserve(std::max<uint64_t>(n, 64), hipHostMallocDefault));
+        direct = mapped_host(p->h_sc.get());
         if (!direct) return MSV_ERR_HIP;
     }
-    if (!direct) MSV_HIP(ensure(p->d_scores, p->d_scores_cap, n));
-    float* const dsc = direct ? direct : p->d_scores;
-    MSV_HIP(ensure(p->d_order, p->d_order_cap, n));
-    if (p->h_off_cap < n + P + 8 + res_words) {  // pinned: the offsets H2D is a true async DMA (+ the error word)
-        if (p->h_off) (void)hipHostFree(p->h_off);
-        p->h_off = nullptr;
-        p->h_off_cap = 0;
-        MSV_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_off), (n + P + 8 + res_words) * sizeof(uint64_t),
-                              hipHostMallocDefault));
-        p->h_off_cap = n + P + 8 + res_words;
-    }
+    if (!direct) MSV_HIP(p->d_scores.reserve(n));
+    float* const dsc = direct ? direct : p->d_scores.get();
+    MSV_HIP(p->d_order.reserve(n));
+    // pinned: the offsets H2D is a true async DMA (+ the error word)
+    MSV_HIP(p->h_off.reserve(n + P + 8 + res_words, hipHostMallocDefault));
     uint32_t* h_err = reinterpret_cast<uint32_t*>(p->h_off + n + P + res_words);
     const uint8_t* const d_small_res = reinterpret_cast<const uint8_t*>(p->d_off + n + P);  // SMALL: residues
     const bool pipe = P > 1 && !zres;
     hipStream_t cs[2] = {st, st}, cp = st;
-    // On an early error return, copies reading the pinned h_off (rewritten by the next call) and
-    // kernels writing the staging buffers may still be queued: drain every stream used first.
-    struct Drain {
-        hipStream_t* cs;
-        hipStream_t* cp;
-        bool armed = true;
-        ~Drain() {
-            if (!armed) return;
-            (void)hipStreamSynchronize(cs[0]);
-            (void)hipStreamSynchronize(cs[1]);
-            (void)hipStreamSynchronize(*cp);
-        }
-    } drain{cs, &cp};
     if (pipe) {
-        if (!p->stream2) MSV_HIP(hipStreamCreateWithFlags(&p->stream2, hipStreamNonBlocking));
-        if (!p->copy_stream) MSV_HIP(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
+        MSV_HIP(p->stream2.create(hipStreamNonBlocking));
+        MSV_HIP(p->copy_stream.create(hipStreamNonBlocking));
         cs[1] = p->pipe_streams == 2 ? p->stream2 : st;
         cp = p->copy_stream;
+    }
+    // On an early error return, copies reading the pinned h_off (rewritten by the next call) and
+    // kernels writing the staging buffers may still be queued: drain every stream used first.
+    msvrt::StreamDrain drain(cs[0], cs[1], cp);
+    if (pipe) {
         while (p->events.size() < P + 4) {
-            hipEvent_t e = nullptr;
-            MSV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToDevice));
-            p->events.push_back(e);
+            msvrt::Event e;
+            MSV_HIP(e.create(hipEventDisableTiming | hipEventReleaseToDevice));
+            p->events.push_back(std::move(e));
         }
         // fork: both helper streams start after the caller's stream's earlier work
         MSV_HIP(hipEventRecord(p->events[P + 2], st));
@@ -1230,7 +1016,7 @@ msv_status msv_score_batch(msv_profile* p, const uint8_t* residues, const uint64
         // scores in page-locked memory: every error leaves a score that is +inf or NaN (scan_scores), so
         // the error word is read only on that rare path (its D2H was a blit launch + 4 us per call)
         MSV_HIP(hipStreamSynchronize(st));  // also: the pinned h_off is rewritten by the next call
-        drain.armed = false;
+        drain.disarm();
         if (staged_scores) std::memcpy(scores, p->h_sc, n * sizeof(float));
         if (scan_scores(scores, n) == MSV_OK) return MSV_OK;
         const msv_status e = check_word(p, st, kHostErrWord);  // reads, clears and reports this call's bits
@@ -1239,7 +1025,7 @@ msv_status msv_score_batch(msv_profile* p, const uint8_t* residues, const uint64
     MSV_HIP(hipMemcpyAsync(scores, p->d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipMemcpyAsync(h_err, p->d_words + kHostErrWord, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipStreamSynchronize(st));  // also: the pinned h_off is rewritten by the next call
-    drain.armed = false;
+    drain.disarm();
     if (*h_err == 0) return MSV_OK;
     return check_word(p, st, kHostErrWord);  // reads, clears and reports this call's error bits
 }
@@ -1248,39 +1034,30 @@ msv_status msv_score_batch_async(msv_profile* p, const uint8_t* residues, const 
                                  float* scores, uint64_t* ticket) {
     if (!p || !ticket || (n && (!offsets || !scores))) return MSV_ERR_INVALID_ARGUMENT;
     *ticket = 0;
-    uint64_t maxL = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-        if (offsets[s + 1] < offsets[s]) return MSV_ERR_INVALID_ARGUMENT;
-        maxL = std::max<uint64_t>(maxL, offsets[s + 1] - offsets[s]);
-    }
-    const uint64_t total = n ? offsets[n] - offsets[0] : 0;
+    uint64_t maxL = 0, total = 0;
+    msv_status s = csr_extent(offsets, n, &maxL, &total);
+    if (s != MSV_OK) return s;
     if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
     // one launch per call: split larger batches (or use msv_score_batch)
-    if (total >= kChunkBytes || n >= (1ull << 32) - (1ull << 24)) return MSV_ERR_INVALID_ARGUMENT;
+    if (total >= kChunkBytes || n >= kMaxLaunchSeqs) return MSV_ERR_INVALID_ARGUMENT;
     auto& a = p->async[p->next_ticket % kAsyncSlots];
     if (a.pending) return MSV_ERR_INVALID_ARGUMENT;  // that slot's call has not been waited for
-    msv_status s = msv_profile_reserve_length(p, maxL);
+    s = msv_profile_reserve_length(p, maxL);
     if (s != MSV_OK) return s;
     DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    if (!p->copy_stream) MSV_HIP(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
-    if (!p->offsets_stream) MSV_HIP(hipStreamCreateWithFlags(&p->offsets_stream, hipStreamNonBlocking));
-    if (!a.copied) MSV_HIP(hipEventCreateWithFlags(&a.copied, hipEventDisableTiming));
-    if (!a.off_copied) MSV_HIP(hipEventCreateWithFlags(&a.off_copied, hipEventDisableTiming));
-    if (!a.done) MSV_HIP(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
-    if (!a.h_err) MSV_HIP(hipHostMalloc(reinterpret_cast<void**>(&a.h_err), 64, hipHostMallocDefault));
-    MSV_HIP(ensure(a.d_res, a.res_cap, std::max<uint64_t>(total, 1)));
-    MSV_HIP(ensure(a.d_off, a.off_cap, n + 1));
+    MSV_HIP(p->copy_stream.create(hipStreamNonBlocking));
+    MSV_HIP(p->offsets_stream.create(hipStreamNonBlocking));
+    MSV_HIP(a.copied.create(hipEventDisableTiming));
+    MSV_HIP(a.off_copied.create(hipEventDisableTiming));
+    MSV_HIP(a.done.create(hipEventDisableTiming));
+    MSV_HIP(a.h_err.reserve(64 / sizeof(uint32_t), hipHostMallocDefault));
+    MSV_HIP(a.d_res.reserve(std::max<uint64_t>(total, 1)));
+    MSV_HIP(a.d_off.reserve(n + 1));
     float* const direct = n ? mapped_host(scores) : nullptr;
-    if (!direct) MSV_HIP(ensure(a.d_sc, a.sc_cap, std::max<uint64_t>(n, 1)));
-    MSV_HIP(ensure(a.d_ord, a.ord_cap, std::max<uint64_t>(n, 1)));
-    if (a.h_cap < n + 1) {
-        if (a.h_off) (void)hipHostFree(a.h_off);
-        a.h_off = nullptr;
-        a.h_cap = 0;
-        MSV_HIP(hipHostMalloc(reinterpret_cast<void**>(&a.h_off), (n + 1) * sizeof(uint64_t), hipHostMallocDefault));
-        a.h_cap = n + 1;
-    }
+    if (!direct) MSV_HIP(a.d_sc.reserve(std::max<uint64_t>(n, 1)));
+    MSV_HIP(a.d_ord.reserve(std::max<uint64_t>(n, 1)));
+    MSV_HIP(a.h_off.reserve(n + 1, hipHostMallocDefault));
     const uint64_t base = n ? offsets[0] : 0;
     for (uint64_t i = 0; i <= n; ++i) a.h_off[i] = n ? offsets[i] - base : 0;
     const int slot = static_cast<int>(&a - p->async);
@@ -1288,18 +1065,11 @@ msv_status msv_score_batch_async(msv_profile* p, const uint8_t* residues, const 
     // Consecutive calls alternate over two compute streams, so a call's kernel fills the CUs that the
     // previous call's drain tail frees instead of starting after the whole previous kernel.
     const bool odd = (p->next_ticket & 1) != 0;
-    if (odd && !p->stream2) MSV_HIP(hipStreamCreateWithFlags(&p->stream2, hipStreamNonBlocking));
+    if (odd) MSV_HIP(p->stream2.create(hipStreamNonBlocking));
     hipStream_t cp = p->copy_stream, co = p->offsets_stream, cs = odd ? p->stream2 : p->stream;
     // On an error return after the first enqueue, copies reading this slot's pinned offsets (rewritten by
     // the slot's next call) may still be queued: drain the call's streams first.
-    struct Drain {
-        hipStream_t s[3];
-        bool armed = true;
-        ~Drain() {
-            if (armed)
-                for (hipStream_t x : s) (void)hipStreamSynchronize(x);
-        }
-    } drain{{co, cp, cs}};
+    msvrt::StreamDrain drain(co, cp, cs);
     // copy streams: this call's inputs (they overlap the earlier calls' kernels on the compute streams).
     // Nothing but copies goes on them: a kernel there (the order, as in round 2) waits for the running MSV
     // grid to drain before it can start, and every later call's copies queued behind it.  The offsets
@@ -1321,7 +1091,7 @@ msv_status msv_score_batch_async(msv_profile* p, const uint8_t* residues, const 
     MSV_HIP(hipStreamWaitEvent(cs, a.copied, 0));
     if (n) {
         s = launch_batch(p, total ? a.d_res : p->d_dummy, std::max<uint64_t>(total, 1), a.d_off, n,
-                         sort ? a.d_ord : nullptr, direct ? direct : a.d_sc, cs, true, d_err);
+                         sort ? a.d_ord.get() : nullptr, direct ? direct : a.d_sc, cs, true, d_err);
         if (s != MSV_OK) return s;
         if (!direct) MSV_HIP(hipMemcpyAsync(scores, a.d_sc, n * sizeof(float), hipMemcpyDeviceToHost, cs));
     }
@@ -1330,7 +1100,7 @@ msv_status msv_score_batch_async(msv_profile* p, const uint8_t* residues, const 
         MSV_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t), cs));
     }
     MSV_HIP(hipEventRecord(a.done, cs));
-    drain.armed = false;
+    drain.disarm();
     a.direct = direct ? scores : nullptr;
     a.n = n;
     a.ticket = p->next_ticket++;
@@ -1541,12 +1311,8 @@ static msv_status score_grid_device(msv_profile* const* profiles, uint32_t n_pro
         if (fv && fv->grid_fn)
             return grid_fused(profiles, n_profiles, fv, d_residues, residues_len, d_offsets, n, d_order, d_scores, cs);
     }
-    hipEvent_t fork = nullptr;
-    MSV_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
-    struct EventGuard {
-        hipEvent_t e;
-        ~EventGuard() { (void)hipEventDestroy(e); }
-    } fork_guard{fork};
+    msvrt::Event fork;
+    MSV_HIP(fork.create(hipEventDisableTiming));
     MSV_HIP(hipEventRecord(fork, cs));
     // Largest models first: their launches are the longest, and with more streams than hardware queues
     // (HIP's default is 4) the launches queued behind them are the short ones.
@@ -1557,7 +1323,7 @@ static msv_status score_grid_device(msv_profile* const* profiles, uint32_t n_pro
     });
     for (const uint32_t i : launch_order) {
         msv_profile* p = profiles[i];
-        if (!p->done) MSV_HIP(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
+        MSV_HIP(p->done.create(hipEventDisableTiming));
         hipStream_t ps = p->stream == cs ? cs : p->stream;
         if (ps != cs) MSV_HIP(hipStreamWaitEvent(ps, fork, 0));
         const msv_status s = launch_batch(p, d_residues, residues_len, d_offsets, n, d_order,
@@ -1584,22 +1350,19 @@ msv_status msv_score_grid(msv_profile* const* profiles, uint32_t n_profiles, con
     for (uint32_t i = 0; i < n_profiles; ++i)
         if (!profiles[i] || profiles[i]->device != profiles[0]->device) return MSV_ERR_INVALID_ARGUMENT;
     if (n == 0) return MSV_OK;
-    uint64_t maxL = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-        if (offsets[s + 1] < offsets[s]) return MSV_ERR_INVALID_ARGUMENT;
-        maxL = std::max<uint64_t>(maxL, offsets[s + 1] - offsets[s]);
-    }
-    const uint64_t bytes = offsets[n] - offsets[0];
+    uint64_t maxL = 0, bytes = 0;
+    msv_status s = csr_extent(offsets, n, &maxL, &bytes);
+    if (s != MSV_OK) return s;
     if (bytes && !residues) return MSV_ERR_INVALID_ARGUMENT;
-    if (bytes >= kChunkBytes || n >= (1ull << 32) - (1ull << 24)) {  // huge batch: per profile, chunked
+    if (bytes >= kChunkBytes || n >= kMaxLaunchSeqs) {  // huge batch: per profile, chunked
         for (uint32_t i = 0; i < n_profiles; ++i) {
-            const msv_status s = msv_score_batch(profiles[i], residues, offsets, n, scores + i * n, stream);
+            s = msv_score_batch(profiles[i], residues, offsets, n, scores + i * n, stream);
             if (s != MSV_OK) return s;
         }
         return MSV_OK;
     }
     for (uint32_t i = 0; i < n_profiles; ++i) {
-        const msv_status s = msv_profile_reserve_length(profiles[i], maxL);
+        s = msv_profile_reserve_length(profiles[i], maxL);
         if (s != MSV_OK) return s;
     }
     msv_profile* p0 = profiles[0];
@@ -1617,24 +1380,13 @@ msv_status msv_score_grid(msv_profile* const* profiles, uint32_t n_profiles, con
     const uint8_t* const zbase = (bytes && p0->zero_copy) ? mapped_host(residues) : nullptr;
     const uint8_t* const zres = zbase ? zbase + offsets[0] : nullptr;
     float* const direct = mapped_host(scores);
-    if (!zres) MSV_HIP(ensure(p0->d_res, p0->d_res_cap, std::max<uint64_t>(bytes, 1)));
-    MSV_HIP(ensure(p0->d_off, p0->d_off_cap, n + 1));
-    MSV_HIP(ensure(p0->d_order, p0->d_order_cap, n));
-    if (!direct) MSV_HIP(ensure(p0->d_scores, p0->d_scores_cap, total));
-    if (p0->h_off_cap < n + 8) {  // pinned: the offsets H2D is a true async DMA
-        if (p0->h_off) (void)hipHostFree(p0->h_off);
-        p0->h_off = nullptr;
-        p0->h_off_cap = 0;
-        MSV_HIP(hipHostMalloc(reinterpret_cast<void**>(&p0->h_off), (n + 8) * sizeof(uint64_t), hipHostMallocDefault));
-        p0->h_off_cap = n + 8;
-    }
-    struct Drain {  // an early error return leaves nothing queued that reads h_off or the staging buffers
-        hipStream_t st;
-        bool armed = true;
-        ~Drain() {
-            if (armed) (void)hipStreamSynchronize(st);
-        }
-    } drain{st};
+    if (!zres) MSV_HIP(p0->d_res.reserve(std::max<uint64_t>(bytes, 1)));
+    MSV_HIP(p0->d_off.reserve(n + 1));
+    MSV_HIP(p0->d_order.reserve(n));
+    if (!direct) MSV_HIP(p0->d_scores.reserve(total));
+    MSV_HIP(p0->h_off.reserve(n + 8, hipHostMallocDefault));  // pinned: the offsets H2D is a true async DMA
+    // an early error return leaves nothing queued that reads h_off or the staging buffers
+    msvrt::StreamDrain drain(st);
     for (uint64_t k = 0; k <= n; ++k) p0->h_off[k] = offsets[k] - offsets[0];
     const uint8_t* d_res = zres ? zres : p0->d_res;
     if (bytes && !zres) MSV_HIP(hipMemcpyAsync(p0->d_res, residues + offsets[0], bytes, hipMemcpyHostToDevice, st));
@@ -1642,14 +1394,14 @@ msv_status msv_score_grid(msv_profile* const* profiles, uint32_t n_profiles, con
     // (a fused cooperative grid runs one workgroup per sequence: no dequeue order to sort; residues read
     // in place never take it)
     const bool sort = fused_coop_variant(profiles, n_profiles, n, zres != nullptr) == nullptr;
-    msv_status s = sort ? msv_order_longest_first(p0, p0->d_off, n, p0->d_order, st) : MSV_OK;
+    s = sort ? msv_order_longest_first(p0, p0->d_off, n, p0->d_order, st) : MSV_OK;
     if (s != MSV_OK) return s;
     float* const dsc = direct ? direct : p0->d_scores;
     s = score_grid_device(profiles, n_profiles, bytes ? d_res : p0->d_dummy, std::max<uint64_t>(bytes, 1), p0->d_off,
-                          n, sort ? p0->d_order : nullptr, dsc, st, zres != nullptr);
+                          n, sort ? p0->d_order.get() : nullptr, dsc, st, zres != nullptr);
     if (s != MSV_OK) return s;
     if (!direct) MSV_HIP(hipMemcpyAsync(scores, p0->d_scores, total * sizeof(float), hipMemcpyDeviceToHost, st));
-    drain.armed = false;
+    drain.disarm();
     MSV_HIP(hipStreamSynchronize(st));  // pageable host buffers above
     // This call's errors show in its scores (+inf: bad residue, NaN: too long), so the profiles' latched
     // error words are read back only when there is one (a 4-byte read-back per profile is a blit kernel
@@ -1737,8 +1489,8 @@ msv_status msv_score_fasta_device(msv_profile* p, const msv_fasta_device* fasta,
     if (s != MSV_OK) return s;
     DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    MSV_HIP(ensure(p->d_scores, p->d_scores_cap, n));
-    MSV_HIP(ensure(p->d_order, p->d_order_cap, n));
+    MSV_HIP(p->d_scores.reserve(n));
+    MSV_HIP(p->d_order.reserve(n));
     const uint64_t* d_off = msv_fasta_device_offsets(fasta);
     s = msv_order_longest_first(p, d_off, n, p->d_order, p->stream);
     if (s != MSV_OK) return s;

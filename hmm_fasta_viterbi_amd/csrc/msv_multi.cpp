@@ -18,7 +18,12 @@
 #include <thread>
 #include <vector>
 
+#include "hip_rt.h"
 #include "msv.h"
+
+using msvrt::DeviceBuffer;
+using msvrt::DeviceGuard;
+using msvrt::kChunkBytes;  // per launch (msv_score_batch_device)
 
 // msv_device.cpp (library-internal): whether page-locked residues are read in place for this model and size.
 extern "C" bool msv_in_place_wins(const msv_profile* p, uint64_t bytes);
@@ -29,50 +34,22 @@ extern "C" msv_status msv_score_batch_host_residues(msv_profile* p, const uint8_
 
 namespace {
 
-constexpr uint64_t kChunkBytes = (1ull << 32) - (1ull << 20);  // per launch (msv_score_batch_device)
-
-msv_status hip_status(hipError_t e) {
-    if (e == hipSuccess) return MSV_OK;
-    if (e == hipErrorOutOfMemory) return MSV_ERR_OUT_OF_MEMORY;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return MSV_ERR_NO_DEVICE;
-    return MSV_ERR_HIP;
-}
-
-#define MM_HIP(call)                                 \
-    do {                                             \
-        hipError_t e_ = (call);                      \
-        if (e_ != hipSuccess) return hip_status(e_); \
-    } while (0)
 #define MM_NCCL(call)                                 \
     do {                                              \
         if ((call) != ncclSuccess) return MSV_ERR_RCCL; \
     } while (0)
 
-template <typename T>
-hipError_t grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t n = std::max<size_t>(need, 1);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-}
-
 struct Rank {
     msv_profile* profile = nullptr;
     int device = -1;
-    hipStream_t stream = nullptr;
+    // (declared before the buffers: a rank's members go in reverse order, the stream last, with the rank's
+    // device current -- msv_multi_destroy)
+    msvrt::Stream stream;
     ncclComm_t comm = nullptr;
-    uint8_t* d_res = nullptr;
-    size_t res_cap = 0;
-    uint64_t* d_off = nullptr;
-    size_t off_cap = 0;
-    uint32_t* d_ord = nullptr;
-    size_t ord_cap = 0;
-    float* d_sc = nullptr;
-    size_t sc_cap = 0;
+    DeviceBuffer<uint8_t> d_res;
+    DeviceBuffer<uint64_t> d_off;
+    DeviceBuffer<uint32_t> d_ord;
+    DeviceBuffer<float> d_sc;
     std::vector<uint64_t> h_off;  // rebased offsets of the shard's current launch
 };
 
@@ -80,23 +57,10 @@ struct Rank {
 
 struct msv_multi {
     std::vector<Rank> ranks;
-    float* d_all = nullptr;  // device 0: every score, input order
-    size_t all_cap = 0;
+    DeviceBuffer<float> d_all;  // device 0: every score, input order
 };
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 // msv_debug_multi_no_alias: make pinned_alias fail, so the copy fallback below runs (tests).
 std::atomic<bool> g_no_alias{false};
@@ -109,19 +73,8 @@ std::atomic<bool> g_no_alias{false};
 // when the call fails, nullptr sends the shard through the copy path (enqueue_shard), which
 // msv_debug_multi_no_alias forces in the GPU tests (bitwise against one launch).
 const uint8_t* pinned_alias(const uint8_t* host) {
-    hipPointerAttribute_t at{};
-    void* h = const_cast<uint8_t*>(host);
-    if (!host || g_no_alias.load(std::memory_order_relaxed) || hipPointerGetAttributes(&at, h) != hipSuccess ||
-        at.type != hipMemoryTypeHost) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return static_cast<const uint8_t*>(d);
+    if (!host || g_no_alias.load(std::memory_order_relaxed)) return nullptr;
+    return msvrt::mapped_host(host);
 }
 
 // Upload shard [first, last) to rank r's device and enqueue its order + kernel launches (one per
@@ -130,7 +83,7 @@ msv_status enqueue_shard(Rank& r, const uint8_t* residues, const uint64_t* offse
     DeviceGuard g(r.device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     const uint64_t cn = last - first;
-    MM_HIP(grow(r.d_sc, r.sc_cap, cn));
+    MSV_HIP(r.d_sc.reserve(cn));
     // (copied instead where the kernel would outrun the in-place reads: small models, large shards)
     const uint8_t* const zres =
         msv_in_place_wins(r.profile, offsets[last] - offsets[first]) ? pinned_alias(residues) : nullptr;
@@ -140,25 +93,25 @@ msv_status enqueue_shard(Rank& r, const uint8_t* residues, const uint64_t* offse
         while (b < last && offsets[b + 1] - offsets[a] < kChunkBytes) ++b;
         if (offsets[b] - offsets[a] >= kChunkBytes) return MSV_ERR_SEQUENCE_TOO_LONG;
         const uint64_t n = b - a, base = offsets[a], bytes = offsets[b] - base;
-        if (!zres) MM_HIP(grow(r.d_res, r.res_cap, std::max<uint64_t>(bytes, 1)));
-        MM_HIP(grow(r.d_off, r.off_cap, n + 1));
-        MM_HIP(grow(r.d_ord, r.ord_cap, n));
+        if (!zres) MSV_HIP(r.d_res.reserve(std::max<uint64_t>(bytes, 1)));
+        MSV_HIP(r.d_off.reserve(n + 1));
+        MSV_HIP(r.d_ord.reserve(n));
         r.h_off.resize(n + 1);
         for (uint64_t i = 0; i <= n; ++i) r.h_off[i] = offsets[a + i] - base;
-        MM_HIP(hipMemcpyAsync(r.d_off, r.h_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, r.stream));
-        if (bytes && !zres) MM_HIP(hipMemcpyAsync(r.d_res, residues + base, bytes, hipMemcpyHostToDevice, r.stream));
+        MSV_HIP(hipMemcpyAsync(r.d_off, r.h_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, r.stream));
+        if (bytes && !zres) MSV_HIP(hipMemcpyAsync(r.d_res, residues + base, bytes, hipMemcpyHostToDevice, r.stream));
         msv_status s = msv_order_longest_first(r.profile, r.d_off, n, r.d_ord, r.stream);
         if (s != MSV_OK) return s;
-        const uint8_t* src = (zres && bytes) ? zres + base : (bytes ? r.d_res : nullptr);
+        const uint8_t* src = (zres && bytes) ? zres + base : (bytes ? r.d_res.get() : nullptr);
         if (!src) {  // an all-empty chunk still needs one readable byte
-            MM_HIP(grow(r.d_res, r.res_cap, 1));
+            MSV_HIP(r.d_res.reserve(1));
             src = r.d_res;
         }
         s = (zres && bytes ? msv_score_batch_host_residues : msv_score_batch_device)(
             r.profile, src, std::max<uint64_t>(bytes, 1), r.d_off, n, r.d_ord, r.d_sc + (a - first), r.stream);
         if (s != MSV_OK) return s;
         // h_off (pageable) is rewritten by the next chunk: let this chunk's copy finish first
-        if (b < last) MM_HIP(hipStreamSynchronize(r.stream));
+        if (b < last) MSV_HIP(hipStreamSynchronize(r.stream));
         a = b;
     }
     return MSV_OK;
@@ -182,15 +135,11 @@ void msv_multi_destroy(msv_multi* m) {
         DeviceGuard g(r.device);
         if (r.stream) (void)hipStreamSynchronize(r.stream);
         if (r.comm) (void)ncclCommDestroy(r.comm);
-        (void)hipFree(r.d_res);
-        (void)hipFree(r.d_off);
-        (void)hipFree(r.d_ord);
-        (void)hipFree(r.d_sc);
-        if (r.stream) (void)hipStreamDestroy(r.stream);
+        const Rank released = std::move(r);  // its buffers, then its stream, freed here under its device
     }
     if (!m->ranks.empty()) {
         DeviceGuard g(m->ranks[0].device);
-        (void)hipFree(m->d_all);
+        m->d_all.reset();
     }
     delete m;
 }
@@ -214,7 +163,7 @@ msv_status msv_multi_create(msv_profile* const* profiles, uint32_t n_profiles, m
         r.profile = profiles[k];
         r.device = devs[k];
         DeviceGuard g(r.device);
-        if (!g.ok || hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking) != hipSuccess) {
+        if (!g.ok || r.stream.create(hipStreamNonBlocking) != hipSuccess) {
             msv_multi_destroy(m);
             return MSV_ERR_NO_DEVICE;
         }
@@ -234,15 +183,13 @@ msv_status msv_multi_score_batch(msv_multi* m, const uint8_t* residues, const ui
                                  float* scores) {
     if (!m || (n && (!offsets || !scores))) return MSV_ERR_INVALID_ARGUMENT;
     if (n == 0) return MSV_OK;
-    uint64_t maxL = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-        if (offsets[s + 1] < offsets[s]) return MSV_ERR_INVALID_ARGUMENT;
-        maxL = std::max<uint64_t>(maxL, offsets[s + 1] - offsets[s]);
-    }
-    if (offsets[n] > offsets[0] && !residues) return MSV_ERR_INVALID_ARGUMENT;
+    uint64_t maxL = 0, total = 0;
+    msv_status s = msvrt::csr_extent(offsets, n, &maxL, &total);
+    if (s != MSV_OK) return s;
+    if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
     const uint32_t R = static_cast<uint32_t>(m->ranks.size());
     std::vector<uint64_t> b(R + 1);
-    msv_status s = msv_shard_bounds(offsets, n, R, b.data());
+    s = msv_shard_bounds(offsets, n, R, b.data());
     if (s != MSV_OK) return s;
     for (Rank& r : m->ranks) {
         s = msv_profile_reserve_length(r.profile, maxL);
@@ -251,7 +198,7 @@ msv_status msv_multi_score_batch(msv_multi* m, const uint8_t* residues, const ui
     {
         DeviceGuard g(m->ranks[0].device);
         if (!g.ok) return MSV_ERR_NO_DEVICE;
-        MM_HIP(grow(m->d_all, m->all_cap, n));
+        MSV_HIP(m->d_all.reserve(n));
     }
     // 1. every rank uploads its shard and enqueues order + kernel, concurrently (one thread each)
     std::vector<msv_status> st(R, MSV_OK);
@@ -287,8 +234,8 @@ msv_status msv_multi_score_batch(msv_multi* m, const uint8_t* residues, const ui
     // 3. one D2H from device 0, then each rank's latched kernel errors
     {
         DeviceGuard g(m->ranks[0].device);
-        MM_HIP(hipMemcpyAsync(scores, m->d_all, n * sizeof(float), hipMemcpyDeviceToHost, m->ranks[0].stream));
-        MM_HIP(hipStreamSynchronize(m->ranks[0].stream));
+        MSV_HIP(hipMemcpyAsync(scores, m->d_all, n * sizeof(float), hipMemcpyDeviceToHost, m->ranks[0].stream));
+        MSV_HIP(hipStreamSynchronize(m->ranks[0].stream));
     }
     for (Rank& r : m->ranks) {
         s = msv_profile_check(r.profile, r.stream);

@@ -16,15 +16,27 @@
 #include <new>
 #include <vector>
 
+#include "hip_rt.h"
+#include "host_cpu.h"
 #include "launch_ring.h"
 #include "msv.h"
 #include "msv_kernel.h"
 #include "vit_kernel.h"
 
+using msvrt::csr_extent;
+using msvrt::DeviceBuffer;
+using msvrt::DeviceGuard;
+using msvrt::hip_status;
+
+// table_layout.cpp builds the tables without vit_kernel.h
+static_assert(vitk::kRows == 20 && vitk::kTransitions == 7 && vitk::kLanes == 64, "table_layout.cpp's shape");
+static_assert(vitk::MM_IN == 0 && vitk::IM_IN == 1 && vitk::DM_IN == 2 && vitk::MI == 3 && vitk::II == 4 &&
+                  vitk::MD_IN == 5 && vitk::DD_IN == 6,
+              "table_layout.cpp's slot arrays");
+
 namespace {
 
 constexpr uint32_t kDefaultMaxLength = 131072;
-constexpr float kNinf = -std::numeric_limits<float>::infinity();
 // d_words: [2k, 2k+1] = launch slot k's dequeue counters {next index, leavers} (zero between launches),
 // [kErrWord] = sticky error bits of device launches (msv_vit_profile_check), [kHostErrWord] = the error bits
 // of the synchronous host calls, which report and clear only their own, [kSelWord] = msv_vit_filter_batch's
@@ -34,31 +46,6 @@ constexpr int kErrWord = 2 * kLaunchSlots;
 constexpr int kHostErrWord = kErrWord + 1;
 constexpr int kSelWord = kHostErrWord + 1;
 constexpr int kWords = kSelWord + 1;
-
-struct Guard {
-    int prev = -1;
-    bool ok = false;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~Guard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-msv_status hip_status(hipError_t e) {
-    if (e == hipSuccess) return MSV_OK;
-    if (e == hipErrorOutOfMemory) return MSV_ERR_OUT_OF_MEMORY;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return MSV_ERR_NO_DEVICE;
-    return MSV_ERR_HIP;
-}
-
-#define VIT_HIP(call)                                \
-    do {                                             \
-        hipError_t e_ = (call);                      \
-        if (e_ != hipSuccess) return hip_status(e_); \
-    } while (0)
 
 msv_status err_status(uint32_t err) {
     if (err & msvk::kErrBadResidue) return MSV_ERR_BAD_RESIDUE;
@@ -92,126 +79,57 @@ struct msv_vit_profile {
     std::vector<float> msc, isc_tab, tsc;  // host copies (re-laid when the variant changes)
     const vitk::VitVariant* v = nullptr;
     uint32_t blocks = 0;                // persistent grid of a full launch
-    float2* d_etab = nullptr;           // [20][S/2][64]
-    float2* d_itab = nullptr;           // [20][S/2][64] (isc)
-    float2* d_ttab = nullptr;           // [7][S/2][64]
-    float2* d_lentab = nullptr;
+    DeviceBuffer<float2> d_etab;        // [20][S/2][64]
+    DeviceBuffer<float2> d_itab;        // [20][S/2][64] (isc)
+    DeviceBuffer<float2> d_ttab;        // [7][S/2][64]
+    DeviceBuffer<float2> d_lentab;
     uint32_t lentab_n = 0;
-    uint32_t* d_words = nullptr;        // kWords, see kLaunchSlots
+    DeviceBuffer<uint32_t> d_words;     // kWords, see kLaunchSlots
     msvrt::LaunchRing<kLaunchSlots> kernels;  // the launch slots' streams and events
-    hipStream_t stream = nullptr;
+    msvrt::Stream stream;
     hipStream_t bound = nullptr;        // msv_vit_profile_bind_stream: a caller stream kept alive while bound
     // msv_vit_score_batch / msv_vit_filter_batch staging
-    uint8_t* d_res = nullptr;
-    size_t res_cap = 0;
-    uint64_t* d_off = nullptr;
-    size_t off_cap = 0;
-    float* d_sc = nullptr;
-    size_t sc_cap = 0;
-    float* d_msc_out = nullptr;
-    size_t msc_out_cap = 0;
-    uint32_t* d_sel = nullptr;
-    size_t sel_cap = 0;
-    uint32_t* d_ord = nullptr;
-    size_t ord_cap = 0;
+    DeviceBuffer<uint8_t> d_res;
+    DeviceBuffer<uint64_t> d_off;
+    DeviceBuffer<float> d_sc;
+    DeviceBuffer<float> d_msc_out;
+    DeviceBuffer<uint32_t> d_sel;
+    DeviceBuffer<uint32_t> d_ord;
     hipEvent_t time_start = nullptr, time_stop = nullptr;  // msv_vit_debug_time_next_launch
     uint64_t* d_stamps = nullptr;                          // msv_vit_debug_set_stamps (tools only)
 };
 
 namespace {
 
-template <typename T>
-hipError_t ensure(T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t n = std::max<size_t>(need, 1);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-}
-
-// Kernel layouts of the variant's tables (vit_kernel.h): slot q of (virtual) lane l is state k = l * S + q + 1;
-// chunk c of a lane holds slots 2c, 2c + 1 as one float2, lanes contiguous (a team's 64 * team virtual lanes;
-// an odd S leaves the last chunk's second slot unused).
+// Lays the variant's tables out (msv_host::vit_tables) and uploads them, all three or none: each goes into a
+// fresh buffer, and the profile adopts them together.
 msv_status install(msv_vit_profile* p, const vitk::VitVariant* v) {
-    const int S = v->S, C2 = v->chunks(), L64 = vitk::kLanes * v->team;
-    const uint32_t M = p->model_length, K = M - 1;
-    const size_t row2 = static_cast<size_t>(C2) * L64;
-    auto state = [&](int l, int q) -> uint32_t { return static_cast<uint32_t>(l * S + q + 1); };
-    std::vector<float2> et(vitk::kRows * row2), it(p->isc ? vitk::kRows * row2 : 0), tt(vitk::kTransitions * row2);
-    for (int r = 0; r < vitk::kRows; ++r)
-        for (int c = 0; c < C2; ++c)
-            for (int l = 0; l < L64; ++l) {
-                float e2[2], i2[2];
-                for (int h = 0; h < 2; ++h) {
-                    const uint32_t k = 2 * c + h < S ? state(l, 2 * c + h) : K + 1;  // (unused slot)
-                    e2[h] = k <= K ? p->msc[static_cast<size_t>(r) * M + k] : kNinf;
-                    i2[h] = (p->isc && k < K) ? p->isc_tab[static_cast<size_t>(r) * M + k] : 0.0f;
-                }
-                et[(r * C2 + c) * L64 + l] = make_float2(e2[0], e2[1]);
-                if (p->isc) it[(r * C2 + c) * L64 + l] = make_float2(i2[0], i2[1]);
-            }
-    // per-slot transition arrays (vitk::MM_IN .. DD_IN); file order m->m m->i m->d i->m i->i d->m d->d
-    enum { MM, MI, MD, IM, II, DM, DD };
-    auto slot_t = [&](int j, uint32_t k) -> float {
-        if (k > K) return kNinf;  // padding slots
-        const float* tin = p->tsc.data() + static_cast<size_t>(k - 1) * 7;  // node k-1 -> node k
-        const float* tout = p->tsc.data() + static_cast<size_t>(k) * 7;     // node k -> I(k)
-        switch (j) {
-            case vitk::MM_IN: return k >= 2 ? tin[MM] : kNinf;
-            case vitk::IM_IN: return k >= 2 ? tin[IM] : kNinf;
-            case vitk::DM_IN: return k >= 2 ? tin[DM] : kNinf;
-            case vitk::MI: return k < K ? tout[MI] : kNinf;
-            case vitk::II: return k < K ? tout[II] : kNinf;
-            case vitk::MD_IN: return k >= 2 ? tin[MD] : kNinf;
-            case vitk::DD_IN: return k >= 2 ? tin[DD] : kNinf;
-        }
-        return kNinf;
+    const msv_host::VitTables t = msv_host::vit_tables(p->msc.data(), p->isc_tab.data(), p->tsc.data(), p->model_length,
+                                                       v->S, v->team, p->isc);
+    auto upload = [](DeviceBuffer<float2>& d, const std::vector<float>& pairs) {
+        return d.replace_with(reinterpret_cast<const float2*>(pairs.data()), pairs.size() / 2);
     };
-    for (int j = 0; j < vitk::kTransitions; ++j)
-        for (int c = 0; c < C2; ++c)
-            for (int l = 0; l < L64; ++l)
-                tt[(j * C2 + c) * L64 + l] = make_float2(slot_t(j, state(l, 2 * c)),
-                                                         slot_t(j, 2 * c + 1 < S ? state(l, 2 * c + 1) : K + 1));
-
-    float2 *de = nullptr, *di = nullptr, *dt = nullptr;
+    DeviceBuffer<float2> de, di, dt;
     hipError_t e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&de), et.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&dt), tt.size() * sizeof(float2))) != hipSuccess ||
-        (p->isc && (e = hipMalloc(reinterpret_cast<void**>(&di), it.size() * sizeof(float2))) != hipSuccess) ||
-        (e = hipMemcpy(de, et.data(), et.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(dt, tt.data(), tt.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (p->isc && (e = hipMemcpy(di, it.data(), it.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess)) {
-        (void)hipFree(de);
-        (void)hipFree(di);
-        (void)hipFree(dt);
+    if ((e = upload(de, t.et)) != hipSuccess || (e = upload(dt, t.tt)) != hipSuccess ||
+        (p->isc && (e = upload(di, t.it)) != hipSuccess))
         return hip_status(e);
-    }
     int per_cu = 0, cus = 0;
     if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn, v->waves * 64, 0)) != hipSuccess ||
-        (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device)) != hipSuccess) {
-        (void)hipFree(de);
-        (void)hipFree(di);
-        (void)hipFree(dt);
+        (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device)) != hipSuccess)
         return hip_status(e);
-    }
     // the previous tables may still be read by a launch in flight on any stream
     if (p->d_etab || p->d_ttab) (void)hipDeviceSynchronize();
-    (void)hipFree(p->d_etab);
-    (void)hipFree(p->d_itab);
-    (void)hipFree(p->d_ttab);
-    p->d_etab = de;
-    p->d_itab = di;
-    p->d_ttab = dt;
+    p->d_etab = std::move(de);
+    p->d_itab = std::move(di);
+    p->d_ttab = std::move(dt);
     p->v = v;
     p->blocks = static_cast<uint32_t>(std::max(1, per_cu) * std::max(1, cus));
     return MSV_OK;
 }
 
 hipStream_t stream_of(const msv_vit_profile* p, void* stream) {
-    return stream ? static_cast<hipStream_t>(stream) : p->stream;
+    return stream ? static_cast<hipStream_t>(stream) : static_cast<hipStream_t>(p->stream);
 }
 
 // Every launch takes the next counter slot (a slot whose previous launch ran on another stream is reused
@@ -225,7 +143,7 @@ msv_status launch(msv_vit_profile* p, const uint8_t* d_residues, const uint64_t*
     if (n >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
     vitk::VitArgs a{};
     a.etab = p->d_etab;
-    a.itab = p->d_itab ? p->d_itab : p->d_etab;
+    a.itab = p->d_itab ? p->d_itab.get() : p->d_etab.get();
     a.ttab = p->d_ttab;
     a.residues = d_residues;
     a.offsets = d_offsets;
@@ -250,26 +168,26 @@ msv_status launch(msv_vit_profile* p, const uint8_t* d_residues, const uint64_t*
         p->time_start = p->time_stop = nullptr;
     }
     int k = 0;
-    VIT_HIP(p->kernels.acquire(st, &k));
+    MSV_HIP(p->kernels.acquire(st, &k));
     a.counter = p->d_words + 2 * k;
     // a slot's counters are put back to zero by the last wave of every launch; a failed launch may leave
     // them dirty, so the slot's next launch resets them explicitly
-    if (p->kernels.dirty[k]) VIT_HIP(hipMemsetAsync(a.counter, 0, 2 * sizeof(uint32_t), st));
+    if (p->kernels.dirty[k]) MSV_HIP(hipMemsetAsync(a.counter, 0, 2 * sizeof(uint32_t), st));
     p->kernels.dirty[k] = true;
-    VIT_HIP(vitk::vit_launch(*p->v, blocks, a, st, start, stop));
+    MSV_HIP(vitk::vit_launch(*p->v, blocks, a, st, start, stop));
     p->kernels.dirty[k] = false;
-    VIT_HIP(p->kernels.release(k, st, st == p->stream || (p->bound && st == p->bound)));
+    MSV_HIP(p->kernels.release(k, st, st == p->stream || (p->bound && st == p->bound)));
     return MSV_OK;
 }
 
 // Reads (and clears when set) one error word of the profile on `st`, synchronously.
 msv_status read_errors(msv_vit_profile* p, int word, hipStream_t st) {
     uint32_t err = 0;
-    VIT_HIP(hipMemcpyAsync(&err, p->d_words + word, sizeof(err), hipMemcpyDeviceToHost, st));
-    VIT_HIP(hipStreamSynchronize(st));
+    MSV_HIP(hipMemcpyAsync(&err, p->d_words + word, sizeof(err), hipMemcpyDeviceToHost, st));
+    MSV_HIP(hipStreamSynchronize(st));
     if (err) {
-        VIT_HIP(hipMemsetAsync(p->d_words + word, 0, sizeof(uint32_t), st));
-        VIT_HIP(hipStreamSynchronize(st));
+        MSV_HIP(hipMemsetAsync(p->d_words + word, 0, sizeof(uint32_t), st));
+        MSV_HIP(hipStreamSynchronize(st));
     }
     return err_status(err);
 }
@@ -280,15 +198,8 @@ extern "C" {
 
 void msv_vit_profile_destroy(msv_vit_profile* p) {
     if (!p) return;
-    Guard g(p->device);
+    DeviceGuard g(p->device);
     (void)hipDeviceSynchronize();
-    for (void* d : {static_cast<void*>(p->d_etab), static_cast<void*>(p->d_itab), static_cast<void*>(p->d_ttab),
-                    static_cast<void*>(p->d_lentab), static_cast<void*>(p->d_words), static_cast<void*>(p->d_res),
-                    static_cast<void*>(p->d_off), static_cast<void*>(p->d_sc), static_cast<void*>(p->d_msc_out),
-                    static_cast<void*>(p->d_sel), static_cast<void*>(p->d_ord)})
-        (void)hipFree(d);
-    p->kernels.destroy();
-    if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
 
@@ -297,23 +208,12 @@ msv_status msv_vit_profile_reserve_length(msv_vit_profile* p, uint64_t max_lengt
     if (max_length >= (1ull << 31)) return MSV_ERR_SEQUENCE_TOO_LONG;
     const uint32_t need = static_cast<uint32_t>(max_length) + 1;
     if (need <= p->lentab_n) return MSV_OK;
-    Guard g(p->device);
+    DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     const uint32_t n = std::max(need, p->lentab_n * 2);
     std::vector<float2> host(n);
     for (uint32_t L = 0; L < n; ++L) msv_sequence_transitions(L, &host[L].x, &host[L].y);  // MSV_HMM.cpp:59-64
-    float2* d = nullptr;
-    VIT_HIP(hipMalloc(reinterpret_cast<void**>(&d), n * sizeof(float2)));
-    hipError_t e = hipMemcpy(d, host.data(), n * sizeof(float2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return hip_status(e);
-    }
-    if (p->d_lentab) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(p->d_lentab);
-    }
-    p->d_lentab = d;
+    MSV_HIP(p->d_lentab.replace_with(host.data(), n));
     p->lentab_n = n;
     return MSV_OK;
 }
@@ -333,7 +233,7 @@ msv_status msv_vit_profile_create(int device, const float* match_scores, const f
     if (device < 0 || device >= ndev) return MSV_ERR_NO_DEVICE;
     const vitk::VitVariant* v = pick_variant(model_length - 1, insert_scores != nullptr);
     if (!v) return MSV_ERR_UNSUPPORTED_MODEL;
-    Guard g(device);
+    DeviceGuard g(device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     auto* p = new (std::nothrow) msv_vit_profile;
     if (!p) return MSV_ERR_OUT_OF_MEMORY;
@@ -348,9 +248,8 @@ msv_status msv_vit_profile_create(int device, const float* match_scores, const f
     if (insert_scores) p->isc_tab.assign(insert_scores, insert_scores + 20 * M);
     p->tsc.assign(transition_scores, transition_scores + 7 * M);
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = p->kernels.create_events()) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&p->d_words), kWords * sizeof(uint32_t))) != hipSuccess ||
+    if ((e = p->stream.create(hipStreamNonBlocking)) != hipSuccess ||
+        (e = p->kernels.create_events()) != hipSuccess || (e = p->d_words.reserve(kWords)) != hipSuccess ||
         (e = hipMemset(p->d_words, 0, kWords * sizeof(uint32_t))) != hipSuccess) {
         msv_vit_profile_destroy(p);
         return hip_status(e);
@@ -419,7 +318,7 @@ msv_status msv_vit_profile_set_variant(msv_vit_profile* p, const char* name) {
         if (std::strcmp(all[i].name, name) == 0) {
             if (all[i].isc != p->isc || static_cast<uint32_t>(all[i].states()) < p->model_length - 1)
                 return MSV_ERR_UNSUPPORTED_MODEL;
-            Guard g(p->device);
+            DeviceGuard g(p->device);
             if (!g.ok) return MSV_ERR_NO_DEVICE;
             return install(p, &all[i]);
         }
@@ -432,7 +331,7 @@ msv_status msv_vit_score_batch_device(msv_vit_profile* p, const uint8_t* d_resid
     if (!p || (n && (!d_offsets || !d_scores))) return MSV_ERR_INVALID_ARGUMENT;
     if (n && residues_len && !d_residues) return MSV_ERR_INVALID_ARGUMENT;
     if (d_select_count && !d_select) return MSV_ERR_INVALID_ARGUMENT;
-    Guard g(p->device);
+    DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     return launch(p, d_residues, d_offsets, n, d_select, d_select_count, d_scores, stream_of(p, stream),
                   p->d_words + kErrWord);
@@ -442,9 +341,9 @@ msv_status msv_vit_profile_bind_stream(msv_vit_profile* p, void* stream) {
     if (!p) return MSV_ERR_INVALID_ARGUMENT;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (st == p->bound) return MSV_OK;
-    Guard g(p->device);
+    DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    if (p->bound) VIT_HIP(p->kernels.flush(p->bound));  // the old stream loses its guarantee
+    if (p->bound) MSV_HIP(p->kernels.flush(p->bound));  // the old stream loses its guarantee
     p->bound = st;
     return MSV_OK;
 }
@@ -468,7 +367,7 @@ msv_status msv_vit_debug_set_stamps(msv_vit_profile* p, uint64_t* d_stamps) {
 
 msv_status msv_vit_profile_check(msv_vit_profile* p, void* stream) {
     if (!p) return MSV_ERR_INVALID_ARGUMENT;
-    Guard g(p->device);
+    DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     return read_errors(p, kErrWord, stream_of(p, stream));
 }
@@ -477,27 +376,26 @@ msv_status msv_vit_score_batch(msv_vit_profile* p, const uint8_t* residues, cons
                                float* scores, void* stream) {
     if (!p || (n && (!offsets || !scores))) return MSV_ERR_INVALID_ARGUMENT;
     if (n == 0) return MSV_OK;
-    const uint64_t base = offsets[0], total = offsets[n] - base;
+    const uint64_t base = offsets[0];
+    uint64_t longest = 0, total = 0;
+    msv_status s = csr_extent(offsets, n, &longest, &total);
+    if (s != MSV_OK) return s;
     if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
-    for (uint64_t s = 0; s < n; ++s)
-        if (offsets[s + 1] < offsets[s]) return MSV_ERR_INVALID_ARGUMENT;
-    uint64_t longest = 0;
-    for (uint64_t s = 0; s < n; ++s) longest = std::max(longest, offsets[s + 1] - offsets[s]);
-    Guard g(p->device);
+    DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    msv_status s = msv_vit_profile_reserve_length(p, longest);
+    s = msv_vit_profile_reserve_length(p, longest);
     if (s != MSV_OK) return s;
     hipStream_t st = stream_of(p, stream);
     std::vector<uint64_t> off(offsets, offsets + n + 1);
     for (auto& o : off) o -= base;
-    VIT_HIP(ensure(p->d_res, p->res_cap, total));
-    VIT_HIP(ensure(p->d_off, p->off_cap, n + 1));
-    VIT_HIP(ensure(p->d_sc, p->sc_cap, n));
-    if (total) VIT_HIP(hipMemcpyAsync(p->d_res, residues + base, total, hipMemcpyHostToDevice, st));
-    VIT_HIP(hipMemcpyAsync(p->d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    MSV_HIP(p->d_res.reserve(total));
+    MSV_HIP(p->d_off.reserve(n + 1));
+    MSV_HIP(p->d_sc.reserve(n));
+    if (total) MSV_HIP(hipMemcpyAsync(p->d_res, residues + base, total, hipMemcpyHostToDevice, st));
+    MSV_HIP(hipMemcpyAsync(p->d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     s = launch(p, p->d_res, p->d_off, n, nullptr, nullptr, p->d_sc, st, p->d_words + kHostErrWord);
     if (s != MSV_OK) return s;
-    VIT_HIP(hipMemcpyAsync(scores, p->d_sc, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    MSV_HIP(hipMemcpyAsync(scores, p->d_sc, n * sizeof(float), hipMemcpyDeviceToHost, st));
     return read_errors(p, kHostErrWord, st);
 }
 
@@ -509,7 +407,7 @@ msv_status msv_filter_select_device(int device, const float* d_scores, const uin
     // No default stream here: NULL would be the legacy null stream, unordered with the profiles' own
     // non-blocking streams that msv_score_batch_device / msv_vit_score_batch_device take for NULL.
     if (!stream) return MSV_ERR_INVALID_ARGUMENT;
-    Guard g(device);
+    DeviceGuard g(device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     return hip_status(
@@ -528,35 +426,32 @@ msv_status msv_vit_filter_batch(msv_profile* msv, msv_vit_profile* vit, const ui
     msv_status s = msv_profile_describe(msv, &info);
     if (s != MSV_OK) return s;
     if (info.device != vit->device) return MSV_ERR_INVALID_ARGUMENT;
-    const uint64_t base = offsets[0], total = offsets[n] - base;
+    const uint64_t base = offsets[0];
+    uint64_t longest = 0, total = 0;
+    if ((s = csr_extent(offsets, n, &longest, &total)) != MSV_OK) return s;
     if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
-    uint64_t longest = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) return MSV_ERR_INVALID_ARGUMENT;
-        longest = std::max(longest, offsets[i + 1] - offsets[i]);
-    }
-    if (total >= (1ull << 32) - (1ull << 20)) return MSV_ERR_INVALID_ARGUMENT;  // one launch per stage
-    Guard g(vit->device);
+    if (total >= msvrt::kChunkBytes) return MSV_ERR_INVALID_ARGUMENT;  // one launch per stage
+    DeviceGuard g(vit->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     if ((s = msv_profile_reserve_length(msv, longest)) != MSV_OK) return s;
     if ((s = msv_vit_profile_reserve_length(vit, longest)) != MSV_OK) return s;
     hipStream_t st = vit->stream;
     std::vector<uint64_t> off(offsets, offsets + n + 1);
     for (auto& o : off) o -= base;
-    VIT_HIP(ensure(vit->d_res, vit->res_cap, total));
-    VIT_HIP(ensure(vit->d_off, vit->off_cap, n + 1));
-    VIT_HIP(ensure(vit->d_sc, vit->sc_cap, n));
-    VIT_HIP(ensure(vit->d_msc_out, vit->msc_out_cap, n));
-    VIT_HIP(ensure(vit->d_sel, vit->sel_cap, n));
-    VIT_HIP(ensure(vit->d_ord, vit->ord_cap, n));
-    if (total) VIT_HIP(hipMemcpyAsync(vit->d_res, residues + base, total, hipMemcpyHostToDevice, st));
-    VIT_HIP(hipMemcpyAsync(vit->d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    MSV_HIP(vit->d_res.reserve(total));
+    MSV_HIP(vit->d_off.reserve(n + 1));
+    MSV_HIP(vit->d_sc.reserve(n));
+    MSV_HIP(vit->d_msc_out.reserve(n));
+    MSV_HIP(vit->d_sel.reserve(n));
+    MSV_HIP(vit->d_ord.reserve(n));
+    if (total) MSV_HIP(hipMemcpyAsync(vit->d_res, residues + base, total, hipMemcpyHostToDevice, st));
+    MSV_HIP(hipMemcpyAsync(vit->d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     // MSV over every sequence, longest first
     if ((s = msv_order_longest_first(msv, vit->d_off, n, vit->d_ord, st)) != MSV_OK) return s;
     if ((s = msv_score_batch_device(msv, vit->d_res, total, vit->d_off, n, vit->d_ord, vit->d_msc_out, st)) != MSV_OK)
         return s;
     // survivors (P <= F1) -> Viterbi, all on the device; non-survivors keep -inf (0xff800000)
-    VIT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(vit->d_sc), static_cast<int>(0xff800000u), n, st));
+    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(vit->d_sc.get()), static_cast<int>(0xff800000u), n, st));
     // survivors listed longest first (the MSV launch's order): the Viterbi launch's tail is its shortest ones
     if ((s = msv_filter_select_device(vit->device, vit->d_msc_out, vit->d_off, vit->d_ord, n, msv_mu, msv_lambda, F1,
                                       nullptr, vit->d_sel, vit->d_words + kSelWord, st)) != MSV_OK)
@@ -565,15 +460,15 @@ msv_status msv_vit_filter_batch(msv_profile* msv, msv_vit_profile* vit, const ui
                     vit->d_words + kHostErrWord)) != MSV_OK)
         return s;
     uint32_t count = 0;
-    VIT_HIP(hipMemcpyAsync(msv_scores, vit->d_msc_out, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    VIT_HIP(hipMemcpyAsync(vit_scores, vit->d_sc, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    VIT_HIP(hipMemcpyAsync(&count, vit->d_words + kSelWord, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    MSV_HIP(hipMemcpyAsync(msv_scores, vit->d_msc_out, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    MSV_HIP(hipMemcpyAsync(vit_scores, vit->d_sc, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    MSV_HIP(hipMemcpyAsync(&count, vit->d_words + kSelWord, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     std::vector<uint32_t> sel;
-    VIT_HIP(hipStreamSynchronize(st));
+    MSV_HIP(hipStreamSynchronize(st));
     if (count) {
         sel.resize(count);
-        VIT_HIP(hipMemcpyAsync(sel.data(), vit->d_sel, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        VIT_HIP(hipStreamSynchronize(st));
+        MSV_HIP(hipMemcpyAsync(sel.data(), vit->d_sel, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MSV_HIP(hipStreamSynchronize(st));
     }
     std::fill(passed, passed + n, static_cast<uint8_t>(0));
     for (uint32_t x : sel) passed[x] = 1;

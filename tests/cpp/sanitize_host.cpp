@@ -5,8 +5,9 @@
 // Profile_HMM.cpp:10-11), the FASTA reader (the golden edge cases, first-line / EOF cases -- the
 // reference's sequences.back() on an empty vector, FASTA_protein_sequences.cpp:22 -- and a file large
 // enough for the multi-threaded chunked path), the precompute (MSV_HMM.cpp:35-57) and the CPU DP
-// (MSV_HMM.cpp:74-113) against the golden scores, msv_shard_bounds, and the Viterbi stage's table builder
-// and CPU DP (msv_hmm_viterbi_scores, msv_vit_cpu_score).
+// (MSV_HMM.cpp:74-113) against the golden scores, msv_shard_bounds, the Viterbi stage's table builder
+// and CPU DP (msv_hmm_viterbi_scores, msv_vit_cpu_score), and the kernel-layout tables the device layer
+// uploads (table_layout.cpp: every MSV, cooperative and Viterbi layout, at exact-fit model lengths).
 // Usage: sanitize_host <repo_root>
 #include <dirent.h>
 #include <unistd.h>
@@ -141,6 +142,134 @@ static Parsed parse_text(const std::string& dir, const std::string& name, const 
     }
     std::remove(path.c_str());
     return p;
+}
+
+// ---- kernel-layout tables (table_layout.cpp) ----
+// The expected table is built the other way round from the builders: they walk the table's slots and ask
+// which state belongs there; here every state 1..R is PLACED at the index its layout comment gives, in a
+// table that is otherwise -inf (rows 0-19) and +inf (the poison row), and the two are compared bit for bit.
+// Entry (r, j) of the synthetic score table is the exactly representable r * 4096 + j: no two states share
+// a value.  The tables are heap vectors of exactly 20 x model_length, so a read past either end is ASan's.
+static const float kNinf = -std::numeric_limits<float>::infinity();
+static const float kPinf = std::numeric_limits<float>::infinity();
+
+static std::vector<float> synthetic(uint32_t model_length, float base = 0.0f) {
+    std::vector<float> es(20 * static_cast<size_t>(model_length));
+    for (uint32_t r = 0; r < 20; ++r)
+        for (uint32_t j = 0; j < model_length; ++j)
+            es[r * static_cast<size_t>(model_length) + j] = base + r * 4096.0f + j;
+    return es;
+}
+
+static void same_tables(const char* what, int a, int b, int c, uint32_t R, const std::vector<float>& got,
+                        const std::vector<float>& want) {
+    const bool same = got.size() == want.size() &&
+                      (want.empty() || std::memcmp(got.data(), want.data(), want.size() * 4) == 0);
+    if (!same) std::printf("  %s (%d, %d, %d) R = %u: size %zu vs %zu\n", what, a, b, c, R, got.size(), want.size());
+    CHECK(same);
+}
+
+// [21][S/4][G] float4; split: A [20][sa/4][G] float4, then B [21][G][HBP] float2 (HBP = (S - sa)/2 rounded up to even)
+static void check_variant_layout(int G, int S, int sa) {
+    const uint32_t cap = static_cast<uint32_t>(G * S);
+    for (uint32_t R : {cap, cap - 1, 1u}) {
+        const uint32_t M = R + 1;
+        const std::vector<float> es = synthetic(M);
+        const size_t SA = sa ? sa : S, a_rows = sa ? 20 : 21, a_size = a_rows * (SA / 4) * G * 4;
+        const size_t HB = sa ? (S - sa) / 2 : 0, HBP = (HB + 1) & ~size_t(1), b_size = sa ? 21 * G * HBP * 2 : 0;
+        std::vector<float> want(a_size + b_size, kNinf);
+        if (!sa) std::fill(want.begin() + 20 * (SA / 4) * G * 4, want.begin() + a_size, kPinf);
+        std::fill(want.begin() + a_size + 20 * G * HBP * 2, want.end(), kPinf);
+        for (size_t r = 0; r < 20; ++r)
+            for (uint32_t j = 1; j <= R; ++j) {
+                const size_t gl = (j - 1) / S, w = (j - 1) % S;
+                const size_t at = w < SA ? ((r * (SA / 4) + w / 4) * G + gl) * 4 + w % 4
+                                         : a_size + ((r * G + gl) * HBP + (w - SA) / 2) * 2 + (w - SA) % 2;
+                want[at] = r * 4096.0f + j;
+            }
+        same_tables("msv_variant_table", G, S, sa, R, msv_host::msv_variant_table(es.data(), M, G, S, sa), want);
+    }
+}
+
+// [21][W][sa/2][64] float2, then (sa < S) [21][W][64][S - sa] floats; wave w's slot (l, k) is state
+// w (64 S - halo) - halo + l S + k + 1, so the first `halo` states of wave w > 0 repeat wave w-1's last ones
+static void check_coop_layout(int W, int S, int sa) {
+    const int halo = (16 + S - 1) / S * S;  // msv_coop.hip's variants
+    const uint32_t cap = static_cast<uint32_t>(W * (64 * S - halo));
+    for (uint32_t R : {cap, cap - 1, 1u}) {
+        const uint32_t M = R + 1;
+        const std::vector<float> es = synthetic(M);
+        const size_t H = sa / 2, SB = S - sa, a_size = size_t(21) * W * H * 64 * 2, b_size = size_t(21) * W * 64 * SB;
+        std::vector<float> want(a_size + b_size, kNinf);
+        std::fill(want.begin() + size_t(20) * W * H * 64 * 2, want.begin() + a_size, kPinf);
+        std::fill(want.begin() + a_size + size_t(20) * W * 64 * SB, want.end(), kPinf);
+        size_t placed = 0;
+        for (size_t r = 0; r < 20; ++r)
+            for (uint32_t j = 1; j <= R; ++j)
+                for (int w = 0; w < W; ++w) {
+                    const int64_t local = int64_t(j) - 1 + halo - int64_t(w) * (64 * S - halo);  // slot within wave w
+                    if (local < 0 || local >= 64 * S) continue;
+                    const size_t l = local / S, k = local % S;
+                    const size_t at = k < size_t(sa) ? (((r * W + w) * H + k / 2) * 64 + l) * 2 + k % 2
+                                                     : a_size + ((r * W + w) * 64 + l) * SB + (k - sa);
+                    want[at] = r * 4096.0f + j;
+                    ++placed;
+                }
+        CHECK(placed >= 20 * size_t(R));  // every state in at least one wave
+        same_tables("msv_coop_table", W, S, sa, R, msv_host::msv_coop_table(es.data(), M, W, S, sa, halo), want);
+    }
+}
+
+// et / it [20][C2][64 team] float2, tt [7][C2][64 team] float2, C2 = (S + 1) / 2: state k = l S + q + 1 is half
+// q % 2 of chunk q / 2 of lane l.  Slot arrays (vit_kernel.h): MM_IN IM_IN DM_IN MI II MD_IN DD_IN, from the file
+// order m->m m->i m->d i->m i->i d->m d->d of node k-1 (the _IN ones, k >= 2) or node k (MI, II, k < K).
+static void check_vit_layout(int S, int team, bool isc) {
+    const uint32_t cap = static_cast<uint32_t>(64 * S * team);
+    for (uint32_t K : {cap, cap - 1, 1u}) {
+        const uint32_t M = K + 1;
+        const std::vector<float> msc = synthetic(M), ins = synthetic(M, 100000.0f);
+        std::vector<float> tsc(7 * static_cast<size_t>(M));
+        for (size_t i = 0; i < tsc.size(); ++i) tsc[i] = -static_cast<float>(i + 1);
+        const size_t C2 = (S + 1) / 2, L = size_t(64) * team, rows = C2 * L * 2;
+        std::vector<float> et(20 * rows, kNinf), it(isc ? 20 * rows : 0, 0.0f), tt(7 * rows, kNinf);
+        static const int from_prev[7] = {0, 3, 5, -1, -1, 2, 6}, from_self[7] = {-1, -1, -1, 1, 4, -1, -1};
+        for (uint32_t k = 1; k <= K; ++k) {
+            const size_t l = (k - 1) / S, q = (k - 1) % S, at = ((q / 2) * L + l) * 2 + q % 2;
+            for (size_t r = 0; r < 20; ++r) {
+                et[r * rows + at] = r * 4096.0f + k;
+                if (isc && k < K) it[r * rows + at] = 100000.0f + r * 4096.0f + k;
+            }
+            for (size_t j = 0; j < 7; ++j) {
+                if (from_prev[j] >= 0 && k >= 2) tt[j * rows + at] = tsc[(k - 1) * size_t(7) + from_prev[j]];
+                if (from_self[j] >= 0 && k < K) tt[j * rows + at] = tsc[k * size_t(7) + from_self[j]];
+            }
+        }
+        const msv_host::VitTables t =
+            msv_host::vit_tables(msc.data(), isc ? ins.data() : nullptr, tsc.data(), M, S, team, isc);
+        same_tables("vit_tables et", S, team, isc, K, t.et, et);
+        same_tables("vit_tables it", S, team, isc, K, t.it, it);
+        same_tables("vit_tables tt", S, team, isc, K, t.tt, tt);
+    }
+}
+
+static void check_layouts() {
+    // (G, S) and (G, S, sa) of the generated variant lists, (waves, S, sa) of msv_coop.hip's, (S, team) of the
+    // Viterbi families (vit_w2_s13_ga4, vit_w2_s12_ga4, vit_w1_s22_ea / vit_s22_t0gi)
+    check_variant_layout(4, 28, 0);
+    check_variant_layout(16, 8, 0);
+    check_variant_layout(64, 24, 0);
+    check_variant_layout(32, 62, 60);  // HB = 1: the padded half
+    check_variant_layout(64, 34, 32);
+    check_coop_layout(4, 2, 2);
+    check_coop_layout(4, 6, 6);
+    check_coop_layout(4, 8, 6);
+    check_coop_layout(4, 10, 6);
+    for (bool isc : {false, true}) {
+        check_vit_layout(13, 2, isc);
+        check_vit_layout(12, 2, isc);
+        check_vit_layout(22, 1, isc);
+    }
+    std::printf("  table layouts: 5 MSV, 4 cooperative and 3 Viterbi geometries at 3 model lengths each\n");
 }
 
 int main(int argc, char** argv) {
@@ -307,6 +436,10 @@ int main(int argc, char** argv) {
             msv_hmm_destroy(h);
         }
     }
+
+    // 8. the kernel-layout table builders (table_layout.cpp) on compiled geometries, at R = capacity,
+    // capacity - 1 and 1 real states
+    check_layouts();
 
     rmdir(dir.c_str());
     if (failures) {

@@ -217,6 +217,44 @@ def test_small_host_calls_staged():
     e.close()
 
 
+def test_buffers_regrow_between_calls_of_different_sizes():
+    """Batches of 1, 300 and 1 sequences (lengths 1..60) in that order on the SAME handles, so every staging
+    buffer is allocated small, regrown, then reused larger than needed: score_batch with pageable arrays, with
+    msv_host_alloc arrays, score_batch_async + wait, score_grid over two profiles (the MSV handle listed
+    twice) and the Viterbi host batch, each bitwise against the CPU oracle.  Then both handles are destroyed,
+    created again, and score the 1-sequence batch once more."""
+    hmm = msv.Profile_HMM(profile_path("100.hmm"))
+    o = OracleProfile("100")
+    batches = [random_batch(610 + k, n, 1, 60) for k, n in enumerate((1, 300, 1))]
+    want = [(o.score_batch(c, f), o.vit_score_batch(c, f)) for c, f in batches]
+
+    def pinned(a):
+        p = msv.pinned_empty(a.shape, a.dtype)
+        p[...] = a
+        return p
+
+    def score_all(e, v, k):
+        (c, f), (w_msv, w_vit) = batches[k], want[k]
+        n = len(f) - 1
+        assert np.array_equal(bits(e.score_batch(codes=c, offsets=f)), bits(w_msv)), k
+        got = e.score_batch(codes=pinned(c), offsets=pinned(f), out=msv.pinned_empty(n, np.float32))
+        assert np.array_equal(bits(got), bits(w_msv)), k
+        assert np.array_equal(bits(e.wait(e.score_batch_async(c, f))), bits(w_msv)), k
+        grid = msv.score_grid([e, e], codes=c, offsets=f)
+        assert np.array_equal(bits(grid), bits(np.stack([w_msv, w_msv]))), k
+        assert np.array_equal(bits(v.score_batch(codes=c, offsets=f)), bits(w_vit)), k
+
+    e, v = msv.MSV_HMM(hmm), msv.Viterbi_HMM(hmm)
+    for k in range(3):
+        score_all(e, v, k)
+    e.close()
+    v.close()
+    e, v = msv.MSV_HMM(hmm), msv.Viterbi_HMM(hmm)
+    score_all(e, v, 0)
+    e.close()
+    v.close()
+
+
 def test_one_profile_on_two_streams_without_sync():
     """launches of one profile on different streams with no synchronisation between them
     (a device call on a torch stream, then the host API on the library's stream, then two more

@@ -1,9 +1,11 @@
 """Host sanitizer builds (ASan/UBSan on the host CPU path; TSan for the chunked,
 multi-threaded FASTA reader).  `make asan` / `make tsan` in hmm_fasta_viterbi_amd/csrc build the
-host-only translation units (parsers, precompute, CPU DP, shard bounds) with plain g++ and run
+host-only translation units (parsers, precompute, CPU DP, shard bounds, the kernel-layout table
+builders) with plain g++ and run
 tests/cpp/test_parsers.cpp and tests/cpp/sanitize_host.cpp under them: the golden scores of all 24
 profiles, the golden FASTA edge cases, first-line / EOF cases, truncated .hmm files, a 40 MiB file
-through the chunked reader.  Any sanitizer report aborts the run (halt_on_error)."""
+through the chunked reader, every MSV / cooperative / Viterbi table layout at exact-fit model lengths.
+Any sanitizer report aborts the run (halt_on_error)."""
 import os
 import subprocess
 
