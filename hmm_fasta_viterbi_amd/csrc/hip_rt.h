@@ -16,12 +16,13 @@
 #include <utility>
 
 #include "msv.h"
+#include "msv_plan.h"
 
 namespace msvrt {
 
-// Every launch addresses < 2^32 residue bytes and fewer than kMaxLaunchSeqs sequences.
-constexpr uint64_t kChunkBytes = (1ull << 32) - (1ull << 20);
-constexpr uint64_t kMaxLaunchSeqs = (1ull << 32) - (1ull << 24);
+// Every launch addresses < 2^32 residue bytes and fewer than kMaxLaunchSeqs sequences (msv_plan.h).
+using msvplan::kChunkBytes;
+using msvplan::kMaxLaunchSeqs;
 
 struct DeviceGuard {
     int prev = -1;
@@ -49,6 +50,18 @@ inline msv_status hip_status(hipError_t e) {
         hipError_t e_ = (call);                             \
         if (e_ != hipSuccess) return msvrt::hip_status(e_); \
     } while (0)
+
+// The persistent grid that fills `device` with `kernel` at `threads` per block: the blocks one CU holds times
+// the CUs.  When only the occupancy query fails, *blocks is one block per CU (0 when the CU count is unknown).
+inline hipError_t resident_blocks(int device, const void* kernel, int threads, int* blocks) {
+    int cus = 0, per_cu = 0;
+    *blocks = 0;
+    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e != hipSuccess) return e;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0);
+    *blocks = cus * (e == hipSuccess ? std::max(1, per_cu) : 1);
+    return e;
+}
 
 // Validates a CSR (offsets non-decreasing) and finds its longest sequence and its residue count.
 inline msv_status csr_extent(const uint64_t* offsets, uint64_t n, uint64_t* maxL, uint64_t* total) {

@@ -14,6 +14,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "hip_rt.h"
@@ -25,7 +26,7 @@ struct LaunchRing {
     Event done[N];
     hipStream_t last[N] = {};  // nullptr: never launched
     bool recorded[N] = {};     // done[k] covers the slot's last launch
-    bool dirty[N] = {};        // a launch failed after the slot's counters were touched
+    bool dirty[N] = {};        // the slot's device words are not known to be zero (run)
     uint32_t next = 0;
 
     // Creates every slot's event up front (created lazily, the first N launches of a fresh profile
@@ -70,6 +71,21 @@ struct LaunchRing {
         last[k] = st;
         recorded[k] = !lazy;
         return lazy ? hipSuccess : hipEventRecord(done[k], st);
+    }
+    // One launch on the next slot, whose device words are base[k * words .. (k + 1) * words): zero between
+    // launches (the kernel puts them back), so they are zeroed here only when dirty -- fresh memory, or a launch
+    // that failed after they were touched.  launch(the slot's words) enqueues the kernel on `st`.
+    template <class Launch>
+    hipError_t run(hipStream_t st, bool lazy, uint32_t* base, size_t words, Launch launch) {
+        int k = 0;
+        hipError_t e = acquire(st, &k);
+        if (e != hipSuccess) return e;
+        uint32_t* const slot = base + static_cast<size_t>(k) * words;
+        if (dirty[k] && (e = hipMemsetAsync(slot, 0, words * sizeof(uint32_t), st)) != hipSuccess) return e;
+        dirty[k] = true;
+        if ((e = launch(slot)) != hipSuccess) return e;
+        dirty[k] = false;
+        return release(k, st, lazy);
     }
     // Records the pending lazy events of stream `st` (before it stops being guaranteed alive).
     hipError_t flush(hipStream_t st) {

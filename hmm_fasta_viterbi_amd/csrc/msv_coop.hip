@@ -63,9 +63,9 @@ __global__ __launch_bounds__(W * 64) void msv_coop_grid_kernel(const GridArgs g)
                 "msv_coop_w" #W_ "_s" #S_ "_a" #SA_, SA_,                                                     \
                 reinterpret_cast<const void*>(&msv_coop_grid_kernel<W_, S_, SA_>)}
 
-// 448 / 960 / 1464 states with the whole table in LDS; 1984 / 2480 with the split table.
-static const CoopVariant kCoop[] = {MSV_COOP_VARIANT(4, 2), MSV_COOP_VARIANT(4, 4), MSV_COOP_VARIANT(4, 6),
-                                    MSV_COOP_SPLIT_VARIANT(4, 8, 6), MSV_COOP_SPLIT_VARIANT(4, 10, 6)};
+static const CoopVariant kCoop[] = {
+#include "msv_coop_variants.inc"
+};
 
 const CoopVariant* coop_variants(int* count) {
     *count = static_cast<int>(sizeof(kCoop) / sizeof(kCoop[0]));

@@ -8,12 +8,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -24,7 +24,11 @@
 #include "launch_ring.h"
 #include "msv.h"
 #include "msv_kernel.h"
+#include "msv_plan.h"
 
+using msvplan::kLaunchSlots;
+using msvplan::kPipelineMin;
+using msvplan::plan_pieces;
 using msvrt::csr_extent;
 using msvrt::DeviceBuffer;
 using msvrt::DeviceGuard;
@@ -36,25 +40,23 @@ using msvrt::PinnedBuffer;
 
 // table_layout.cpp builds the tables without msv_kernel.h
 static_assert(msvk::kAminoAcids == 20 && msvk::kPoisonRow == 20 && msvk::kTableRows == 21, "table_layout.cpp's rows");
+static_assert(msvplan::kGridMaxProfiles == msvk::kGridMaxProfiles, "msv_plan.h's fused launch");
 
 namespace {
 
 constexpr uint32_t kDefaultMaxLength = 131072;
 constexpr uint32_t kOrderBins = 4096;  // lengths >= 4095 share the longest bin
-// Every launch of one profile takes the next of kLaunchSlots device counter pairs {next index, waves
+// Every launch of one profile takes the next of kLaunchSlots (msv_plan.h) device counter pairs {next index, waves
 // left} (and, for the longest-first order, the next histogram), so launches on different streams
 // never share a counter; a slot is reused only after its previous launch (an event wait when the
 // streams differ).  d_words: [2k, 2k+1] = slot k's counters, [kErrWord] = sticky error bits,
 // [kErrWord + 1 + a] = the error bits of asynchronous staging slot a (msv_score_batch_async),
 // [kHostErrWord] = the error bits of synchronous host calls (msv_score_batch), which report and clear only
 // their own: bits latched by msv_score_batch_device launches stay for msv_profile_check.
-constexpr int kLaunchSlots = 8;
 constexpr int kAsyncSlots = 3;
 constexpr int kErrWord = 2 * kLaunchSlots;
 constexpr int kHostErrWord = kErrWord + 1 + kAsyncSlots;
 constexpr int kWords = kHostErrWord + 1;
-// Host batches of at least this many residues are scored as a copy/compute pipeline of pieces.
-constexpr uint64_t kPipelineMin = 4ull << 20;
 // Small host calls (pageable residues of at most kSmallCall bytes, at most kSmallCall sequences -- the
 // reference's one-sequence-per-call pattern): residues staged behind the offsets in the pinned offsets
 // buffer and sent in ONE H2D; pageable scores written by the kernel into pinned staging (no D2H).
@@ -84,82 +86,26 @@ std::vector<float2> host_length_table(uint32_t n) {
     return std::vector<float2>(table.begin(), table.begin() + n);
 }
 
-// Estimated issue cost of one row for one sequence: 2.5 VALU per state-slot plus the per-row
-// specials/reduction, times the lanes a sequence occupies.  A BIG table costs little with one
-// sequence per wave (G = 64: wave-uniform LDS/L2 row split) and a lot with 2-4 sequences per wave
-// (generic loads with per-lane address selects); measured on 2405.hmm: 7.4 vs 10.5 ms.
-// A split table (the lane's last S - SA states read from L2 every row) costs the B-table address and
-// loads per row and no class branch, so it also runs two sequences per wave (G = 32).
-double variant_cost(const msvk::Variant& v) {
-    // (G = 64 BIG: 1.15 -- 1901.hmm's 64 x 32 row-class plan measured 1.12 / 2.20 ms against 0.97 / 1.99 ms
-    // for the 64 x 34 split plan at 3 / 2048 sequences, profiles/r02_latency_plans.jsonl)
-    const double big = !v.big ? 1.0 : (v.G == 64 ? 1.15 : 1.6);
-    // G = 64: + permlane32 step, scalar bookkeeping
-    const double row = (v.G == 64 ? 36.0 : 26.0) + (v.sa ? 2.0 : 0.0);
-    return (2.5 * v.S + row) * v.G * big * (v.pf == 2 ? 1.0 : 1.05) * (v.streams == 2 ? 1.15 : 1.0);
-}
-
-// Latency plan for small batches: one sequence per wave (G = 64) so a row is ~40% of the
-// instructions of a 16-lane row; the cheapest such variant covering the model (non-BIG if any).
-const msvk::Variant* pick_latency_variant(uint32_t states) {
-    int count = 0;
-    const msvk::Variant* all = msvk::variants(&count);
-    const msvk::Variant* best = nullptr;
-    for (int i = 0; i < count; ++i) {
-        const msvk::Variant& v = all[i];
-        if (v.G != 64 || static_cast<uint32_t>(v.G * v.S) < states) continue;
-        if (!best || variant_cost(v) < variant_cost(*best)) best = &v;
-    }
-    return best;
-}
-
-// Mid plan for batches between the latency plan's and one round of the main grid: two sequences per
-// wave (G = 32), the cheapest plain (LDS-table, one-stream) variant covering the model.
-const msvk::Variant* pick_mid_variant(uint32_t states) {
-    int count = 0;
-    const msvk::Variant* all = msvk::variants(&count);
-    const msvk::Variant* best = nullptr;
-    for (int i = 0; i < count; ++i) {
-        const msvk::Variant& v = all[i];
-        if (v.G != 32 || v.streams != 1 || v.big || v.sa || static_cast<uint32_t>(v.G * v.S) < states) continue;
-        if (!best || variant_cost(v) < variant_cost(*best)) best = &v;
-    }
-    return best;
-}
-
-// `narrow`: 4-lane groups may be picked.  Their rows are long (16 sequences per wave), which the issue
-// model rewards and which wins once the SIMDs are full, so they are the throughput plan of the smallest
-// profiles (100.hmm x 100k: g4_s28 0.339 vs g16_s8 0.521 ms, x 1M 3.08 vs 4.11 ms) while batches that
-// leave the SIMDs part-empty keep a 16-lane plan (x 10k: 0.138 vs 0.099 ms; install_variant).  8-lane
-// groups stay tuning candidates: on 200.hmm g8_s32 against g16_s16 was 6% slower at 100k, 2% faster
-// at 1M (profiles/r02_small_profiles.jsonl).
-// A whole-row emission ring (PF = S/4: the next row's chunks requested during this row's epilogue) on
-// 16 waves, for 16-lane rows of 16-32 states.
-static bool whole_row_ring(const msvk::Variant& v) {
-    return v.G == 16 && v.streams == 1 && !v.big && !v.sa && v.pf * 4 == v.S && v.S >= 16 && v.S <= 32;
-}
-
-// `whole_row`: whole-row-ring variants are preferred where they exist -- on full batches 1-5% faster
-// than the PF-2 ones (200/300/400/500.hmm x 100k: 0.692/0.827/1.051/1.196 vs 0.708/0.837/1.094/1.259 ms),
-// while below a round of the grid the PF-2 ones hold (500.hmm x 10k: 0.229 vs 0.197 ms;
-// profiles/r02_whole_row_rings.jsonl), so those stay the plan of smaller batches (install_variant).
-const msvk::Variant* pick_variant(uint32_t states, bool narrow, bool whole_row = false) {
-    int count = 0;
-    const msvk::Variant* all = msvk::variants(&count);
-    const msvk::Variant* best = nullptr;
-    auto cost = [&](const msvk::Variant& v) { return variant_cost(v) * (whole_row && whole_row_ring(v) ? 0.9 : 1.0); };
-    for (int i = 0; i < count; ++i) {
-        const msvk::Variant& v = all[i];
-        if (static_cast<uint32_t>(v.G * v.S) < states) continue;
-        // (not for tables of fewer than 80 states: a 28-state lane row would be mostly padding, unmeasured)
-        if (v.G < 16 && !(narrow && v.G == 4 && states >= 80)) continue;
-        if (!best || cost(v) < cost(*best)) best = &v;
-    }
-    return best;
-}
-
 // Launch slots of one profile (see kLaunchSlots and launch_ring.h).
 using LaunchRing = msvrt::LaunchRing<kLaunchSlots>;
+
+// The shapes of msvk::variants() and msvk::coop_variants(), index for index, for the policy (msv_plan.h).
+const msvplan::Tables& plan_tables() {
+    static const msvplan::Tables tables = [] {
+        msvplan::Tables t;
+        int count = 0;
+        const msvk::Variant* all = msvk::variants(&count);
+        for (int i = 0; i < count; ++i) {
+            const msvk::Variant& v = all[i];
+            t.variants.push_back({v.G, v.S, v.waves, v.pf, v.streams, v.sa, v.big, v.grid_fn != nullptr});
+        }
+        const msvk::CoopVariant* coop = msvk::coop_variants(&count);
+        for (int i = 0; i < count; ++i)
+            t.coop.push_back({coop[i].waves, coop[i].S, coop[i].halo, coop[i].sa, coop[i].grid_fn != nullptr});
+        return t;
+    }();
+    return tables;
+}
 
 }  // namespace
 
@@ -181,17 +127,14 @@ struct msv_profile {
     Plan fused;                   // the table in another profile's latency layout (fused grid launches)
     Plan coop;                    // one sequence per workgroup, the row over its waves (msv_coop.hip)
     Plan coop_fused;              // the table in another profile's cooperative layout (fused grid launches)
-    uint64_t coop_max_n = 0;      // batches up to this many sequences take the cooperative plan
+    msvplan::PlanSet chosen;      // which of them exist, and up to how many sequences each is taken (msv_plan.h)
     bool force = false;           // msv_profile_set_variant: main plan for every batch size
-    uint64_t lat_max_n = 0;       // batches up to this many sequences take the latency plan
-    uint64_t mid_max_n = 0;       // batches above lat_max_n and up to this many take the mid plan
     float tr_B_Mk = 0, tr_E_C = 0, tr_E_J = 0;
     std::vector<float> emission_scores;  // host copy [20][model_length] (for re-layout)
     DeviceBuffer<float2> d_lentab;
     uint32_t lentab_n = 0;
     DeviceBuffer<uint32_t> d_words;  // kLaunchSlots x {dequeue counter, waves still running}, sticky error bits
     DeviceBuffer<uint32_t> d_hist;  // kLaunchSlots longest-first counting-sort scratches [hist | cursors]
-    std::array<bool, kLaunchSlots> hist_dirty{};  // histogram not known to be zero (fresh, failed launch)
     DeviceBuffer<uint8_t> d_dummy;  // a readable residue byte for batches with no residues
     LaunchRing kernels, orders;   // launch slots of the MSV kernel and of the order sort
     msvrt::Stream stream;
@@ -282,42 +225,26 @@ static msv_status scan_scores(const float* scores, uint64_t n) {
     return MSV_OK;
 }
 
-// Lays the MSV table out for variant v (msv_host::msv_variant_table) and uploads it.
+// The persistent grid of `kernel` on the device; one block per CU when the occupancy query fails.
+static msv_status grid_blocks(int device, const void* kernel, int waves, int* blocks) {
+    const hipError_t e = msvrt::resident_blocks(device, kernel, waves * 64, blocks);
+    return *blocks > 0 ? MSV_OK : hip_status(e);
+}
+
+// Lays the MSV table out for variant v (msv_host::msv_variant_table), uploads it and sizes the grid.
 static msv_status install_plan(msv_profile* p, const msvk::Variant* v, Plan& plan) {
     const std::vector<float> tab =
         msv_host::msv_variant_table(p->emission_scores.data(), p->model_length, v->G, v->S, v->sa);
     // (the old table may be read by an in-flight launch on any stream the caller used: replace_with)
     MSV_HIP(plan.d_etab.replace_with(reinterpret_cast<const float4*>(tab.data()), tab.size() / 4));
     plan.v = v;
-    hipDeviceProp_t prop;
-    MSV_HIP(hipGetDeviceProperties(&prop, p->device));
-    int per_cu = 0;
-    const hipError_t e =
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(v->fn), v->waves * 64, 0);
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    plan.blocks = prop.multiProcessorCount * per_cu;
     plan.groups_per_block = v->waves * (64 / v->G) * v->streams;
-    return MSV_OK;
+    return grid_blocks(p->device, v->fn, v->waves, &plan.blocks);
 }
 
 static void drop_plan(Plan& plan) {
     if (plan.d_etab) (void)hipDeviceSynchronize();  // may be read by an in-flight launch
     plan = Plan{};
-}
-
-// The cooperative plan (msv_coop.hip) for batches of at most one workgroup per CU: one sequence per
-// workgroup, its row spread over 4 waves (one per SIMD) with halo states and a speculated B.  Installed
-// when a compiled CoopVariant covers the model (the whole table staged in LDS up to 1464 states, the
-// split table -- each lane's last 2-4 states read from L2 -- up to 2480) and
-// tr_E_C == tr_E_J (the reference's nu = 2, MSV_HMM.cpp:49-53), and never under a forced variant.
-// The smallest cooperative variant covering `states`, or nullptr.
-static const msvk::CoopVariant* pick_coop_variant(uint32_t states) {
-    int count = 0;
-    const msvk::CoopVariant* all = msvk::coop_variants(&count);
-    const msvk::CoopVariant* cv = nullptr;
-    for (int i = 0; i < count; ++i)
-        if (static_cast<uint32_t>(all[i].states()) >= states && (!cv || all[i].S < cv->S)) cv = &all[i];
-    return cv;
 }
 
 // Lays p's table out for cooperative variant cv (msv_host::msv_coop_table) into `plan` (d_etab, cv).
@@ -332,148 +259,46 @@ static msv_status install_coop_table(msv_profile* p, const msvk::CoopVariant* cv
     return MSV_OK;
 }
 
-static msv_status install_coop(msv_profile* p) {
-    drop_plan(p->coop);
-    p->coop_max_n = 0;
-    if (p->force || std::memcmp(&p->tr_E_C, &p->tr_E_J, sizeof(float)) != 0) return MSV_OK;
-    const msvk::CoopVariant* cv = pick_coop_variant(p->model_length - 1);
-    if (!cv) return MSV_OK;
-    const msv_status st = install_coop_table(p, cv, p->coop);
-    if (st != MSV_OK) return st;
-    int cus = 0, per_cu = 0;
+// Chooses the profile's plans (msv_plan.h choose; `forced`: the index of the variant msv_profile_set_variant
+// named, or -1) and installs them: every chosen plan's table laid out and uploaded and its grid sized, every
+// other plan dropped.
+static msv_status install_plans(msv_profile* p, int forced) {
+    int cus = 0, count = 0;
     MSV_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cv->fn, cv->waves * 64, 0);
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    p->coop.blocks = cus * per_cu;
-    // Up to where it beats the plan the batch would otherwise take (tools/coop_sweep.py,
-    // profiles/r03_coop_sweep.jsonl; L U[300,500], kernel ms coop / other): 1400.hmm 512 seqs 0.106 /
-    // 0.191, 1024 0.144 / 0.194, 2048 0.272 / 0.198; 1001.hmm 512 0.147 / 0.153; 1901.hmm 1024 0.243 /
-    // 0.264; 2405.hmm (L ~2000) 1024 1.19 / 1.35; 400.hmm (S = 2, 768 workgroups) 512 0.037 / 0.105, 1024
-    // 0.113 / 0.107; 100.hmm (no latency plan) 256 0.056 / 0.074, 512 0.071 / 0.074, 1024 0.099 / 0.074.
-    // So two rounds of the grid for S >= 4, one for S = 2, half of one without a latency plan.
-    const double rounds = (cv->S >= 4 ? 2.0 : 1.0) * (p->lat.v ? 1.0 : 0.5);
-    p->coop_max_n = static_cast<uint64_t>(rounds * p->coop.blocks);
-    return MSV_OK;
-}
-
-// Mid plan (G = 32, two sequences per wave) for G = 16 profiles with S >= 40 (~600-1536 states), taken
-// by batches between the latency plan's range and about one round of the main grid.  There a 16-lane
-// launch runs one partial round of 400-row sequences at ~2-3 waves per SIMD (latency-bound: ~4 ns per
-// instruction per wave), and a 64-lane one needs 2-3 rounds; the 32-lane rows are half as long as the
-// 16-lane ones at twice the waves.  1400.hmm x U[300,500]: 9000 sequences 0.388 ms against 0.458
-// (latency plan) / 0.527 (main), 12000 0.464 vs 0.536 (main); 600.hmm x 6000 0.151 vs 0.245 (latency)
-// / 0.175 (main); 900.hmm x 9000 0.299 vs 0.353 / 0.367 (profiles/r02_mid_plans.jsonl).
-//  * upper end: 0.9 of one round of the main grid, and for S < 64 at most 10,752 sequences (3/4 of the
-//    16,384 at which 16-lane launches fill 4 waves per SIMD: 800.hmm x 12000 ran 0.326 mid vs 0.291
-//    main, while 1400.hmm x 12000 0.464 vs 0.536);
-//  * lower end (the latency plan's new limit): where the 64-lane row stops being much shorter than the
-//    32-lane one -- 15000 x (mid row / latency row - 1) sequences, within 1.5 rounds of the latency
-//    grid: 1400.hmm (136 vs 96 VALU) ~6,100 (x 6000: 0.302 latency vs 0.306 mid), 600.hmm (76 vs 66)
-//    2,270 (x 6000: mid 38% faster), 800.hmm (96 vs 76) 3,950 (x 6000: mid 8% faster).
-// 500.hmm (S = 32) measured no consistent gain (the 32-lane plan won at some sizes and lost 10-15% at
-// others) and keeps two plans.
-static msv_status install_mid(msv_profile* p) {
-    const msvk::Variant* mv = pick_mid_variant(p->model_length - 1);
-    if (!mv || !p->lat.v || p->main.v->G != 16 || p->main.v->S < 40) return MSV_OK;
-    const uint64_t lat_cap = static_cast<uint64_t>(p->lat.blocks) * p->lat.groups_per_block;
-    const uint64_t main_cap = static_cast<uint64_t>(p->main.blocks) * p->main.groups_per_block;
-    const double mid_row = 2.5 * mv->S + 26.0;
-    const double lat_row = 2.5 * p->lat.v->S + 36.0 + (p->lat.v->sa ? 2.0 : 0.0);
-    const uint64_t lat_by_rows = static_cast<uint64_t>(std::max(0.0, 15000.0 * (mid_row / lat_row - 1.0)));
-    const uint64_t lat_max = std::min({p->lat_max_n, lat_cap * 3 / 2, lat_by_rows});
-    const uint64_t mid_max = std::min<uint64_t>(main_cap * 9 / 10, p->main.v->S >= 64 ? ~0ull : 10752);
-    if (mid_max <= lat_max) return MSV_OK;
-    msv_status s = install_plan(p, mv, p->mid);
-    if (s != MSV_OK) return s;
-    p->lat_max_n = lat_max;
-    p->mid_max_n = mid_max;
-    return MSV_OK;
-}
-
-// Main plan for `v`; unless forced, the latency plan (its own table layout) unless it would be the same
-// kernel, and a mid plan (install_mid; or, when the main plan has 4-lane groups, the 16-lane plan for
-// batches that leave the SIMDs part-empty).
-static msv_status install_variant_plans(msv_profile* p, const msvk::Variant* main_v) {
-    msv_status s = install_plan(p, main_v, p->main);
-    if (s != MSV_OK) return s;
-    const uint32_t states = p->model_length - 1;
-    // the 16+-lane plan the latency plan is weighed against, and the plan of batches below one round of
-    // the grid: the main plan itself unless it is narrow (4 lanes) or a whole-row-ring variant
-    const msvk::Variant* v =
-        (main_v->G < 16 || whole_row_ring(*main_v)) && !p->force ? pick_variant(states, false) : main_v;
-    const msvk::Variant* lv = p->force ? nullptr : pick_latency_variant(states);
-    // Worth it only when the 64-lane row is much shorter than the main row (per-row issue cost,
-    // as variant_cost): 1400.hmm 246 vs 96 -> 0.23 vs 0.62 ms at 1024 sequences, 0.37 vs 0.64 at 8192,
-    // even at 16384; 1901.hmm 176 vs 123 -> 0.97 vs 1.29 ms at 3 sequences, 1.99 vs 2.89 at 2048;
-    // 100.hmm 46 vs 46 -> slower at every size (tools/tune.py, profiles/r01_latency_plan.jsonl,
-    // r02_latency_plans.jsonl).
-    const double main_row = 2.5 * v->S + 26.0, lat_row = lv ? 2.5 * lv->S + 36.0 + (lv->sa ? 2.0 : 0.0) : 0.0;
-    const double ratio = lv ? main_row / lat_row : 0.0;
-    drop_plan(p->mid);
-    p->mid_max_n = 0;
-    if (v != main_v) {
-        // Narrow main plan: the 16-lane plan while it would not fill the SIMDs -- 3.5 of its waves per
-        // SIMD, where a 16-lane launch turns issue-bound (100.hmm: 14,336 sequences on 256 CUs; the
-        // crossover measured between 10k and 20k, profiles/r02_small_profiles.jsonl).  Whole-row-ring
-        // main plan: the PF-2 variant up to 3/4 of that (10,752).
-        int cus = 0;
-        MSV_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
-        s = install_plan(p, v, p->mid);
+    const msvk::Variant* all = msvk::variants(&count);
+    const msvk::CoopVariant* coop = msvk::coop_variants(&count);
+    const auto blocks_of = [&](msvplan::Kind kind, int i) {
+        int blocks = 0;
+        if (kind == msvplan::kCoop) (void)grid_blocks(p->device, coop[i].fn, coop[i].waves, &blocks);
+        else (void)grid_blocks(p->device, all[i].fn, all[i].waves, &blocks);
+        return blocks;
+    };
+    const bool same_EJ = std::memcmp(&p->tr_E_C, &p->tr_E_J, sizeof(float)) == 0;
+    const msvplan::PlanSet ps = msvplan::choose(plan_tables(), p->model_length - 1, same_EJ, forced, cus, blocks_of);
+    if (ps.main < 0) return MSV_ERR_UNSUPPORTED_MODEL;
+    p->force = forced >= 0;  // a forced variant runs every batch (tests, tools/tune.py)
+    p->chosen = msvplan::PlanSet{};  // (a failure below leaves every batch on the main plan)
+    const struct {
+        int index;
+        Plan& plan;
+    } plans[] = {{ps.main, p->main}, {ps.lat, p->lat}, {ps.mid, p->mid}};
+    for (const auto& x : plans) {
+        if (x.index < 0) {
+            drop_plan(x.plan);
+            continue;
+        }
+        const msv_status s = install_plan(p, &all[x.index], x.plan);
         if (s != MSV_OK) return s;
-        const double fill = main_v->G < 16 ? 3.5 : 2.625;
-        p->mid_max_n = static_cast<uint64_t>(fill * 4 * cus * (64 / v->G));
     }
-    if (!lv || lv == v || ratio < 1.3) {
-        drop_plan(p->lat);
-        p->lat_max_n = 0;
-        return MSV_OK;
+    if (ps.coop < 0) {
+        drop_plan(p->coop);
+    } else {
+        msv_status s = install_coop_table(p, &coop[ps.coop], p->coop);
+        if (s == MSV_OK) s = grid_blocks(p->device, coop[ps.coop].fn, coop[ps.coop].waves, &p->coop.blocks);
+        if (s != MSV_OK) return s;
     }
-    p->lat_max_n = static_cast<uint64_t>(std::min(12288.0, 4096.0 * ratio));
-    s = install_plan(p, lv, p->lat);
-    if (s != MSV_OK) return s;
-    if (p->mid.v) {
-        p->lat_max_n = std::min(p->lat_max_n, p->mid_max_n);
-        return MSV_OK;
-    }
-    return install_mid(p);
-}
-
-// The main / mid / latency plans, then the cooperative plan in front of them (it needs to know whether a
-// latency plan exists: install_coop).
-static msv_status install_variant(msv_profile* p, const msvk::Variant* main_v) {
-    const msv_status s = install_variant_plans(p, main_v);
-    if (s != MSV_OK) return s;
-    return install_coop(p);
-}
-
-// Pieces of a host batch for msv_score_batch's copy/compute pipeline: cut[k] .. cut[k+1] is piece
-// k's sequence range.  Each piece addresses < kChunkBytes residues and < 2^32 - 2^24 sequences (one
-// launch each).  Batches below kPipelineMin residues are one piece; larger ones start at 1/first_den
-// of the batch (at least 1M residues) and grow `growth`-fold, a short remainder joining the last piece.
-static std::vector<uint64_t> plan_pieces(const uint64_t* offsets, uint64_t n, uint64_t total, uint32_t first_den,
-                                         uint32_t growth) {
-    constexpr uint64_t kMaxSeqs = kMaxLaunchSeqs - 1;
-    std::vector<uint64_t> cut{0};
-    uint64_t want = (total < kPipelineMin || first_den == 0) ? kChunkBytes
-                                                             : std::max<uint64_t>(1ull << 20, total / first_den);
-    uint64_t first = 0;
-    while (first < n) {
-        const uint64_t base = offsets[first];
-        auto end_of = [&](uint64_t budget) {  // last sequence index with offsets[last] - base <= budget
-            const uint64_t* it = std::upper_bound(offsets + first + 1, offsets + n + 1, base + budget);
-            return static_cast<uint64_t>(it - offsets) - 1;
-        };
-        uint64_t last = std::max(end_of(std::min(want, kChunkBytes - 1)), first + 1);  // >= one sequence
-        last = std::min(last, first + kMaxSeqs);
-        // a remainder shorter than this piece joins it (half the next piece at the default growth of 2),
-        // if the chunk limit allows
-        const uint64_t rest = offsets[n] - offsets[last];
-        if (last < n && rest < want && offsets[n] - base < kChunkBytes && n - first <= kMaxSeqs) last = n;
-        cut.push_back(last);
-        first = last;
-        want = std::min(kChunkBytes, std::max<uint32_t>(growth, 1) * want);
-    }
-    return cut;
+    p->chosen = ps;
+    return MSV_OK;
 }
 
 extern "C" {
@@ -520,50 +345,32 @@ msv_status msv_profile_create(int device, const float* emission_scores, uint32_t
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MSV_ERR_NO_DEVICE;
     if (device < 0 || device >= ndev) return MSV_ERR_NO_DEVICE;
-    const uint32_t R = model_length - 1;  // real match states (MSV_HMM.cpp:285)
-    const msvk::Variant* v = pick_variant(R, true, true);
-    if (!v) return MSV_ERR_UNSUPPORTED_MODEL;
-
     DeviceGuard g(device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    auto* p = new (std::nothrow) msv_profile;
+    struct Destroy {
+        void operator()(msv_profile* p) const { msv_profile_destroy(p); }
+    };
+    std::unique_ptr<msv_profile, Destroy> p(new (std::nothrow) msv_profile);  // destroyed on every error return
     if (!p) return MSV_ERR_OUT_OF_MEMORY;
     p->device = device;
     p->model_length = model_length;
     p->tr_B_Mk = tr_B_Mk;
     p->tr_E_C = tr_E_C;
     p->tr_E_J = tr_E_J;
-
     p->emission_scores.assign(emission_scores, emission_scores + static_cast<size_t>(20) * model_length);
-    hipError_t e;
-    if ((e = p->stream.create(hipStreamNonBlocking)) != hipSuccess) {
-        msv_profile_destroy(p);
-        return hip_status(e);
-    }
+    MSV_HIP(p->stream.create(hipStreamNonBlocking));
     // every launch slot's event up front: created lazily, the first kLaunchSlots launches of a fresh
     // profile each paid an event creation (~10 us; 24 of them in one fused grid call)
-    for (LaunchRing* ring : {&p->kernels, &p->orders})
-        if ((e = ring->create_events()) != hipSuccess) {
-            msv_profile_destroy(p);
-            return hip_status(e);
-        }
-    if ((e = p->d_words.reserve(kWords)) != hipSuccess ||
-        (e = hipMemset(p->d_words, 0, kWords * sizeof(uint32_t))) != hipSuccess ||
-        (e = p->d_dummy.reserve(64)) != hipSuccess || (e = hipMemset(p->d_dummy, 0, 64)) != hipSuccess) {
-        msv_profile_destroy(p);
-        return hip_status(e);
-    }
-    msv_status s = install_variant(p, v);
-    if (s != MSV_OK) {
-        msv_profile_destroy(p);
-        return s;
-    }
-    s = msv_profile_reserve_length(p, kDefaultMaxLength - 1);
-    if (s != MSV_OK) {
-        msv_profile_destroy(p);
-        return s;
-    }
-    *out = p;
+    MSV_HIP(p->kernels.create_events());
+    MSV_HIP(p->orders.create_events());
+    MSV_HIP(p->d_words.reserve(kWords));
+    MSV_HIP(hipMemset(p->d_words, 0, kWords * sizeof(uint32_t)));
+    MSV_HIP(p->d_dummy.reserve(64));
+    MSV_HIP(hipMemset(p->d_dummy, 0, 64));
+    msv_status s = install_plans(p.get(), -1);  // (MSV_ERR_UNSUPPORTED_MODEL: no variant covers the model)
+    if (s == MSV_OK) s = msv_profile_reserve_length(p.get(), kDefaultMaxLength - 1);
+    if (s != MSV_OK) return s;
+    *out = p.release();
     return MSV_OK;
 }
 
@@ -588,8 +395,7 @@ msv_status msv_profile_set_variant(msv_profile* p, const char* name) {
         if (static_cast<uint32_t>(all[i].G * all[i].S) < p->model_length - 1) return MSV_ERR_UNSUPPORTED_MODEL;
         DeviceGuard g(p->device);
         if (!g.ok) return MSV_ERR_NO_DEVICE;
-        p->force = true;  // a forced variant runs every batch (tests, tools/tune.py)
-        return install_variant(p, &all[i]);
+        return install_plans(p, i);
     }
     return MSV_ERR_INVALID_ARGUMENT;
 }
@@ -642,7 +448,7 @@ msv_status msv_debug_time_next_launch(msv_profile* p, void* start, void* stop) {
 msv_status msv_debug_set_coop_max_n(msv_profile* p, uint64_t n) {
     if (!p) return MSV_ERR_INVALID_ARGUMENT;
     if (!p->coop.cv) return MSV_ERR_UNSUPPORTED_MODEL;
-    p->coop_max_n = n;
+    p->chosen.coop_max_n = n;
     return MSV_OK;
 }
 
@@ -691,42 +497,62 @@ msv_status msv_profile_describe(const msv_profile* p, msv_kernel_info* out) {
     if (p->lat.v) {
         std::snprintf(out->latency_variant, sizeof(out->latency_variant), "%s", p->lat.v->name);
         out->latency_blocks = static_cast<uint32_t>(p->lat.blocks);
-        out->latency_max_n = p->lat_max_n;
+        out->latency_max_n = p->chosen.lat_max_n;
     }
     if (p->coop.cv) {
         std::snprintf(out->coop_variant, sizeof(out->coop_variant), "%s", p->coop.cv->name);
         out->coop_blocks = static_cast<uint32_t>(p->coop.blocks);
-        out->coop_max_n = p->coop_max_n;
+        out->coop_max_n = p->chosen.coop_max_n;
     }
     if (p->mid.v) {
         std::snprintf(out->mid_variant, sizeof(out->mid_variant), "%s", p->mid.v->name);
         out->mid_blocks = static_cast<uint32_t>(p->mid.blocks);
-        out->mid_max_n = p->mid_max_n;
+        out->mid_max_n = p->chosen.mid_max_n;
     }
     return MSV_OK;
 }
 
-// The plan a launch of n sequences takes: latency (n <= lat_max_n), mid (n <= mid_max_n), else main.
+// The plan a launch of n sequences takes (msv_plan.h which).
 static const Plan& select_plan(const msv_profile* p, uint64_t n, bool latency_ok, bool host_residues = false) {
-    if (!latency_ok) return p->main;
-    // (not for residues read in place over PCIe: its 16-row residue blocks would wait on each one)
-    if (p->coop.cv && n <= p->coop_max_n && !host_residues) return p->coop;
-    if (p->lat.v && n <= p->lat_max_n) return p->lat;
-    if (p->mid.v && n <= p->mid_max_n) return p->mid;
-    return p->main;
+    switch (msvplan::which(p->chosen, n, latency_ok, host_residues)) {
+        case msvplan::kCoop: return p->coop;
+        case msvplan::kLatency: return p->lat;
+        case msvplan::kMid: return p->mid;
+        default: return p->main;
+    }
 }
 
-// A batch that takes the cooperative plan with at most one sequence per workgroup needs no dequeue order
-// (every workgroup scores one sequence whatever the order): the host paths then skip the sort launch.
 static bool order_needless(const msv_profile* p, uint64_t n, bool host_residues) {
-    const Plan& plan = select_plan(p, n, true, host_residues);
-    return plan.cv && n <= static_cast<uint64_t>(plan.blocks);
+    return msvplan::order_needless(p->chosen, n, host_residues, p->coop.blocks);
 }
 
 const char* msv_profile_variant_for(const msv_profile* p, uint64_t n) {
     if (!p || !p->main.v) return "";
     const Plan& plan = select_plan(p, n, true);
     return plan.cv ? plan.cv->name : plan.v->name;
+}
+
+// The kernel arguments of one batch on `plan` of `p`: no stamps, the device launches' error word and (for the
+// kernels that dequeue) counter slot 0 until the caller says otherwise.
+static msvk::KernelArgs kernel_args(const msv_profile* p, const Plan& plan, const uint8_t* d_residues,
+                                    uint64_t residues_len, const uint64_t* d_offsets, uint64_t n,
+                                    const uint32_t* d_order, float* d_scores) {
+    msvk::KernelArgs a{};
+    a.etab = plan.d_etab;
+    a.residues = residues_len ? d_residues : p->d_dummy;
+    a.offsets = d_offsets;
+    a.order = d_order;
+    a.lentab = p->d_lentab;
+    a.scores = d_scores;
+    a.counter = p->d_words;
+    a.errors = p->d_words + kErrWord;
+    a.n = n;
+    a.lentab_n = p->lentab_n;
+    a.tr_B_Mk = p->tr_B_Mk;
+    a.tr_E_C = p->tr_E_C;
+    a.tr_E_J = p->tr_E_J;
+    a.stamps = nullptr;
+    return a;
 }
 
 // One MSV launch.  `latency_ok`: a batch of few sequences may take the latency plan (not for the
@@ -743,56 +569,35 @@ static msv_status launch_batch(msv_profile* p, const uint8_t* d_residues, uint64
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : p->stream;
 
-    msvk::KernelArgs a{};
-    // Small batches take the latency plan: with fewer sequences than ~4 per SIMD the launch lasts
-    // one sequence's rows, and a 64-lane row is far shorter than a 16-lane one.  Mid-size ones (less
-    // than one round of the main grid) take the 32-lane plan where there is one (install_variant).
     const Plan& plan = select_plan(p, n, latency_ok, host_residues);
-    a.etab = plan.d_etab;
-    a.residues = residues_len ? d_residues : p->d_dummy;
-    a.offsets = d_offsets;
-    a.order = d_order;
-    a.lentab = p->d_lentab;
-    a.scores = d_scores;
-    a.n = n;
-    a.lentab_n = p->lentab_n;
-    a.tr_B_Mk = p->tr_B_Mk;
-    a.tr_E_C = p->tr_E_C;
-    a.tr_E_J = p->tr_E_J;
-    a.stamps = p->d_stamps;
+    msvk::KernelArgs a = kernel_args(p, plan, d_residues, residues_len, d_offsets, n, d_order, d_scores);
+    if (d_errors) a.errors = d_errors;
     const bool clock = p->stamp_clock && !host_residues;
+    a.stamps = p->d_stamps;
     if (p->stamp_clock && (plan.cv || !plan.v->clock_fn || host_residues)) a.stamps = nullptr;  // no CLOCK twin
 
     const uint64_t want = (n + plan.groups_per_block - 1) / plan.groups_per_block;
     const int blocks = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(plan.blocks), want));
+    hipEvent_t t0 = p->time_start, t1 = p->time_stop;
+    p->time_start = p->time_stop = nullptr;
     if (plan.cv) {  // the cooperative plan: a workgroup per sequence, no dequeue counter
-        a.errors = d_errors ? d_errors : p->d_words + kErrWord;
-        hipEvent_t t0 = p->time_start, t1 = p->time_stop;
-        p->time_start = p->time_stop = nullptr;
         void* params[] = {&a};
         const dim3 block(static_cast<uint32_t>(plan.cv->waves * 64));
         MSV_HIP(t0 || t1 ? hipExtLaunchKernel(plan.cv->fn, dim3(blocks), block, params, 0, st, t0, t1, 0)
                          : hipLaunchKernel(plan.cv->fn, dim3(blocks), block, params, 0, st));
         return MSV_OK;
     }
-    // A slot's counters (next index, waves left) are zero between launches: zeroed at creation and
-    // put back by the last wave of every launch (msv_kernel.hip).  A failed launch may leave them
-    // dirty, so the slot's next launch resets them explicitly.
-    int k = 0;
-    MSV_HIP(p->kernels.acquire(st, &k));
-    a.counter = p->d_words + 2 * k;
-    a.errors = d_errors ? d_errors : p->d_words + kErrWord;
-    if (p->kernels.dirty[k]) MSV_HIP(hipMemsetAsync(a.counter, 0, 2 * sizeof(uint32_t), st));
-    p->kernels.dirty[k] = true;
-    hipEvent_t t0 = p->time_start, t1 = p->time_stop;
-    p->time_start = p->time_stop = nullptr;
     // the twin of a residue-block variant (rows of <= 40 states) reads 4-byte superblock words, clamped
     // to the buffer only from 4 bytes up: it takes buffers of at least 64 bytes
     const bool wide = plan.v->S <= 40;  // (twins of rows > 40 states prefetch two rows; see zc_fn)
     const bool twin = host_residues && (!wide || (p->zc_wide && residues_len >= 64));
-    MSV_HIP(msvk::launch_variant(*plan.v, dim3(blocks), a, st, t0, t1, twin, clock));
-    p->kernels.dirty[k] = false;
-    MSV_HIP(p->kernels.release(k, st, lazy_stream(p, st)));
+    // A slot's counters (next index, waves left) are zero between launches: zeroed at creation and
+    // put back by the last wave of every launch (msv_kernel.hip).  A failed launch may leave them
+    // dirty, so the slot's next launch resets them explicitly (LaunchRing::run).
+    MSV_HIP(p->kernels.run(st, lazy_stream(p, st), p->d_words.get(), 2, [&](uint32_t* counter) {
+        a.counter = counter;
+        return msvk::launch_variant(*plan.v, dim3(blocks), a, st, t0, t1, twin, clock);
+    }));
     return MSV_OK;
 }
 
@@ -854,20 +659,15 @@ msv_status msv_order_longest_first(msv_profile* p, const uint64_t* d_offsets, ui
     DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : p->stream;
+    constexpr size_t kScratch = msvk::kOrderScratchWords(kOrderBins);
     if (!p->d_hist) {
-        MSV_HIP(p->d_hist.reserve(kLaunchSlots * msvk::kOrderScratchWords(kOrderBins)));
-        p->hist_dirty.fill(true);
+        MSV_HIP(p->d_hist.reserve(kLaunchSlots * kScratch));
+        std::fill(std::begin(p->orders.dirty), std::end(p->orders.dirty), true);  // fresh memory
     }
-    int k = 0;
-    MSV_HIP(p->orders.acquire(st, &k));
     // [histogram | cursors | ticket] per slot; the sort leaves histogram and ticket zeroed for the slot's next use
-    uint32_t* scratch = p->d_hist + static_cast<size_t>(k) * msvk::kOrderScratchWords(kOrderBins);
-    if (p->hist_dirty[k])
-        MSV_HIP(hipMemsetAsync(scratch, 0, msvk::kOrderScratchWords(kOrderBins) * sizeof(uint32_t), st));
-    p->hist_dirty[k] = true;
-    MSV_HIP(msvk::launch_order(d_offsets, n, scratch, kOrderBins, d_order, st));
-    p->hist_dirty[k] = false;
-    MSV_HIP(p->orders.release(k, st, lazy_stream(p, st)));
+    MSV_HIP(p->orders.run(st, lazy_stream(p, st), p->d_hist.get(), kScratch, [&](uint32_t* scratch) {
+        return msvk::launch_order(d_offsets, n, scratch, kOrderBins, d_order, st);
+    }));
     return MSV_OK;
 }
 
@@ -1134,13 +934,6 @@ msv_status msv_profile_wait(msv_profile* p, uint64_t ticket) {
     return MSV_ERR_INVALID_ARGUMENT;  // unknown ticket, or already waited for
 }
 
-// A grid of few sequences (one 64-lane wave each, at most this many waves over all profiles) runs as ONE
-// launch: every profile's batch takes the latency layout of the grid's largest model, so each
-// profile's launch lasts about as long as it would alone, and all of them run at once instead of
-// queueing on the process's hardware queues (4 by default: 24 profiles x 3 sequences of 3,500
-// residues, benchmark_MSV's shape, took 4.05 ms as 24 launches).
-constexpr uint64_t kFusedMaxSeqs = 2048;
-
 // The plan of `p` whose table is in variant v's layout (installing it as p->fused if none is).
 static msv_status plan_in_layout(msv_profile* p, const msvk::Variant* v, const Plan** out) {
     for (const Plan* q : {&p->main, &p->lat, &p->mid, &p->fused})
@@ -1167,28 +960,20 @@ static msv_status coop_plan_in_layout(msv_profile* p, const msvk::CoopVariant* c
     return MSV_OK;
 }
 
-// The cooperative variant a grid of n sequences x these profiles runs fused (grid_coop_fused), or nullptr:
-// a grid of few sequences (n x profiles <= kFusedMaxSeqs), every profile with tr_E_C == tr_E_J and no
-// forced variant, a variant covering the largest model -- and at most as many workgroups per launch (n x
-// the launch's profiles) as the smallest coop_max_n of the listed profiles: the limit of the per-profile
-// cooperative plan (about one workgroup fits a CU, so a launch of more is several rounds of the grid, and
-// past ~2 rounds the cooperative plan loses).  coop_max_n = 0 (no cooperative plan, or
-// msv_debug_set_coop_max_n(0)) turns the fused form off.  Residues read in place over PCIe
-// (host_residues) keep the latency layout, as select_plan does.
-static const msvk::CoopVariant* fused_coop_variant(msv_profile* const* profiles, uint32_t n_profiles, uint64_t n,
-                                                   bool host_residues = false) {
-    if (host_residues || n_profiles < 2 || n * n_profiles > kFusedMaxSeqs) return nullptr;
-    uint32_t states = 0;
-    uint64_t cap = ~0ull;
+// How a grid of n sequences x these profiles runs (msv_plan.h fused_grid).
+static msvplan::GridChoice grid_choice(msv_profile* const* profiles, uint32_t n_profiles, uint64_t n,
+                                       bool host_residues) {
+    std::vector<msvplan::GridProfile> shapes(n_profiles);
+    uint32_t most = 0;  // the most times one handle is listed
     for (uint32_t i = 0; i < n_profiles; ++i) {
         const msv_profile* p = profiles[i];
-        if (p->force || std::memcmp(&p->tr_E_C, &p->tr_E_J, sizeof(float)) != 0) return nullptr;
-        states = std::max(states, p->model_length - 1);
-        cap = std::min(cap, p->coop_max_n);
+        shapes[i] = {p->model_length - 1, p->force, std::memcmp(&p->tr_E_C, &p->tr_E_J, sizeof(float)) == 0,
+                     p->chosen.coop_max_n};
+        uint32_t same = 0;
+        for (uint32_t j = 0; j < n_profiles; ++j) same += profiles[j] == p;
+        most = std::max(most, same);
     }
-    if (static_cast<uint64_t>(std::min<uint32_t>(n_profiles, msvk::kGridMaxProfiles)) * n > cap) return nullptr;
-    const msvk::CoopVariant* cv = pick_coop_variant(states);
-    return cv && cv->grid_fn ? cv : nullptr;
+    return msvplan::fused_grid(plan_tables(), shapes.data(), n_profiles, n, host_residues, most);
 }
 
 // A grid of few sequences on the cooperative plan: ONE msv_coop_grid_kernel launch per 32 profiles, every
@@ -1209,21 +994,8 @@ static msv_status grid_coop_fused(msv_profile* const* profiles, uint32_t n_profi
             const Plan* plan = nullptr;
             const msv_status s = coop_plan_in_layout(p, cv, &plan);
             if (s != MSV_OK) return s;
-            msvk::KernelArgs& a = ga.p[j];
-            a.etab = plan->d_etab;
-            a.residues = residues_len ? d_residues : p->d_dummy;
-            a.offsets = d_offsets;
-            a.order = d_order;
-            a.lentab = p->d_lentab;
-            a.scores = d_scores + static_cast<uint64_t>(first + j) * n;
-            a.n = n;
-            a.lentab_n = p->lentab_n;
-            a.tr_B_Mk = p->tr_B_Mk;
-            a.tr_E_C = p->tr_E_C;
-            a.tr_E_J = p->tr_E_J;
-            a.counter = p->d_words;  // (unused by the cooperative kernel)
-            a.errors = p->d_words + kErrWord;
-            a.stamps = nullptr;
+            ga.p[j] = kernel_args(p, *plan, d_residues, residues_len, d_offsets, n, d_order,
+                                  d_scores + static_cast<uint64_t>(first + j) * n);
         }
         void* params[] = {&ga};
         MSV_HIP(hipLaunchKernel(cv->grid_fn, dim3(count * ga.per_profile), dim3(static_cast<uint32_t>(cv->waves * 64)),
@@ -1249,21 +1021,10 @@ static msv_status grid_fused(msv_profile* const* profiles, uint32_t n_profiles, 
             msv_status s = plan_in_layout(p, v, &plan);
             if (s != MSV_OK) return s;
             msvk::KernelArgs& a = ga.p[j];
-            a.etab = plan->d_etab;
-            a.residues = residues_len ? d_residues : p->d_dummy;
-            a.offsets = d_offsets;
-            a.order = d_order;
-            a.lentab = p->d_lentab;
-            a.scores = d_scores + static_cast<uint64_t>(first + j) * n;
-            a.n = n;
-            a.lentab_n = p->lentab_n;
-            a.tr_B_Mk = p->tr_B_Mk;
-            a.tr_E_C = p->tr_E_C;
-            a.tr_E_J = p->tr_E_J;
-            a.stamps = nullptr;
+            a = kernel_args(p, *plan, d_residues, residues_len, d_offsets, n, d_order,
+                            d_scores + static_cast<uint64_t>(first + j) * n);
             MSV_HIP(p->kernels.acquire(cs, &slot[j]));
             a.counter = p->d_words + 2 * slot[j];
-            a.errors = p->d_words + kErrWord;
             if (p->kernels.dirty[slot[j]]) MSV_HIP(hipMemsetAsync(a.counter, 0, 2 * sizeof(uint32_t), cs));
             p->kernels.dirty[slot[j]] = true;
         }
@@ -1290,27 +1051,14 @@ static msv_status score_grid_device(msv_profile* const* profiles, uint32_t n_pro
     DeviceGuard g(profiles[0]->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     hipStream_t cs = stream ? static_cast<hipStream_t>(stream) : profiles[0]->stream;
-    if (n_profiles > 1 && n * n_profiles <= kFusedMaxSeqs) {
-        uint32_t states = 0;
-        bool forced = false;
-        uint32_t most = 0;  // the most times one handle is listed (each entry takes one of its counter slots)
-        for (uint32_t i = 0; i < n_profiles; ++i) {
-            states = std::max(states, profiles[i]->model_length - 1);
-            forced |= profiles[i]->force;  // msv_profile_set_variant: that variant for every batch
-            uint32_t same = 0;
-            for (uint32_t j = 0; j < n_profiles; ++j) same += profiles[j] == profiles[i];
-            most = std::max(most, same);
-        }
-        const msvk::CoopVariant* cv = fused_coop_variant(profiles, n_profiles, n, host_residues);
-        if (cv)
-            return grid_coop_fused(profiles, n_profiles, cv, d_residues, residues_len, d_offsets, n, d_order, d_scores, cs);
-        // A fused launch holds one counter slot per entry until it ends: a handle listed more often than
-        // it has slots would share a {next, waves left} pair between two sub-grids of one launch.
-        forced |= most > static_cast<uint32_t>(kLaunchSlots);
-        const msvk::Variant* fv = forced ? nullptr : pick_latency_variant(states);
-        if (fv && fv->grid_fn)
-            return grid_fused(profiles, n_profiles, fv, d_residues, residues_len, d_offsets, n, d_order, d_scores, cs);
-    }
+    const msvplan::GridChoice fused = grid_choice(profiles, n_profiles, n, host_residues);
+    int count = 0;
+    if (fused.kind == msvplan::GridChoice::kCoopFused)
+        return grid_coop_fused(profiles, n_profiles, &msvk::coop_variants(&count)[fused.index], d_residues, residues_len,
+                               d_offsets, n, d_order, d_scores, cs);
+    if (fused.kind == msvplan::GridChoice::kLatencyFused)
+        return grid_fused(profiles, n_profiles, &msvk::variants(&count)[fused.index], d_residues, residues_len,
+                          d_offsets, n, d_order, d_scores, cs);
     msvrt::Event fork;
     MSV_HIP(fork.create(hipEventDisableTiming));
     MSV_HIP(hipEventRecord(fork, cs));
@@ -1393,7 +1141,7 @@ msv_status msv_score_grid(msv_profile* const* profiles, uint32_t n_profiles, con
     MSV_HIP(hipMemcpyAsync(p0->d_off, p0->h_off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     // (a fused cooperative grid runs one workgroup per sequence: no dequeue order to sort; residues read
     // in place never take it)
-    const bool sort = fused_coop_variant(profiles, n_profiles, n, zres != nullptr) == nullptr;
+    const bool sort = grid_choice(profiles, n_profiles, n, zres != nullptr).kind != msvplan::GridChoice::kCoopFused;
     s = sort ? msv_order_longest_first(p0, p0->d_off, n, p0->d_order, st) : MSV_OK;
     if (s != MSV_OK) return s;
     float* const dsc = direct ? direct : p0->d_scores;

@@ -114,17 +114,15 @@ msv_status install(msv_vit_profile* p, const vitk::VitVariant* v) {
     if ((e = upload(de, t.et)) != hipSuccess || (e = upload(dt, t.tt)) != hipSuccess ||
         (p->isc && (e = upload(di, t.it)) != hipSuccess))
         return hip_status(e);
-    int per_cu = 0, cus = 0;
-    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn, v->waves * 64, 0)) != hipSuccess ||
-        (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device)) != hipSuccess)
-        return hip_status(e);
+    int blocks = 0;
+    if ((e = msvrt::resident_blocks(p->device, v->fn, v->waves * 64, &blocks)) != hipSuccess) return hip_status(e);
     // the previous tables may still be read by a launch in flight on any stream
     if (p->d_etab || p->d_ttab) (void)hipDeviceSynchronize();
     p->d_etab = std::move(de);
     p->d_itab = std::move(di);
     p->d_ttab = std::move(dt);
     p->v = v;
-    p->blocks = static_cast<uint32_t>(std::max(1, per_cu) * std::max(1, cus));
+    p->blocks = static_cast<uint32_t>(std::max(1, blocks));
     return MSV_OK;
 }
 
@@ -167,16 +165,13 @@ msv_status launch(msv_vit_profile* p, const uint8_t* d_residues, const uint64_t*
         stop = p->time_stop;
         p->time_start = p->time_stop = nullptr;
     }
-    int k = 0;
-    MSV_HIP(p->kernels.acquire(st, &k));
-    a.counter = p->d_words + 2 * k;
     // a slot's counters are put back to zero by the last wave of every launch; a failed launch may leave
-    // them dirty, so the slot's next launch resets them explicitly
-    if (p->kernels.dirty[k]) MSV_HIP(hipMemsetAsync(a.counter, 0, 2 * sizeof(uint32_t), st));
-    p->kernels.dirty[k] = true;
-    MSV_HIP(vitk::vit_launch(*p->v, blocks, a, st, start, stop));
-    p->kernels.dirty[k] = false;
-    MSV_HIP(p->kernels.release(k, st, st == p->stream || (p->bound && st == p->bound)));
+    // them dirty, so the slot's next launch resets them explicitly (LaunchRing::run)
+    const bool lazy = st == p->stream || (p->bound && st == p->bound);
+    MSV_HIP(p->kernels.run(st, lazy, p->d_words.get(), 2, [&](uint32_t* counter) {
+        a.counter = counter;
+        return vitk::vit_launch(*p->v, blocks, a, st, start, stop);
+    }));
     return MSV_OK;
 }
 

@@ -7,7 +7,8 @@
 // enough for the multi-threaded chunked path), the precompute (MSV_HMM.cpp:35-57) and the CPU DP
 // (MSV_HMM.cpp:74-113) against the golden scores, msv_shard_bounds, the Viterbi stage's table builder
 // and CPU DP (msv_hmm_viterbi_scores, msv_vit_cpu_score), and the kernel-layout tables the device layer
-// uploads (table_layout.cpp: every MSV, cooperative and Viterbi layout, at exact-fit model lengths).
+// uploads (table_layout.cpp: every MSV, cooperative and Viterbi layout, at exact-fit model lengths), and the MSV
+// plan policy (msv_plan.cpp) against the plans recorded on the device (tests/golden/msv_plans.json).
 // Usage: sanitize_host <repo_root>
 #include <dirent.h>
 #include <unistd.h>
@@ -18,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <initializer_list>
 #include <limits>
 #include <map>
 #include <random>
@@ -28,6 +30,7 @@
 #include "host_cpu.h"
 #include "msv.h"
 #include "msv_hmm.hpp"
+#include "msv_plan.h"
 
 static int failures = 0;
 #define CHECK(c)                                                              \
@@ -272,6 +275,284 @@ static void check_layouts() {
     std::printf("  table layouts: 5 MSV, 4 cooperative and 3 Viterbi geometries at 3 model lengths each\n");
 }
 
+// ---- the MSV plan policy (msv_plan.cpp) ----
+// The shape tables come from the lists the kernel tables are built from, under macros of this file: index i
+// here is index i of msvk::variants() / msvk::coop_variants(), and the names are the kernels' names.
+struct NamedVariant {
+    msvplan::VariantShape shape;
+    const char* name;
+};
+struct NamedCoop {
+    msvplan::CoopShape shape;
+    const char* name;
+};
+// msv_kernel.h: lds_rows_for(G, S) < kTableRows, the table does not fit the 160 KiB of LDS
+static constexpr bool big_table(int G, int S) { return 163840 / (G * S * 4) < 21; }
+// (the grid kernel exists for the one-sequence-per-wave variants: msv_kernel_impl.h grid_fn)
+#define MSV_VARIANT(G, S, W, P, D) \
+    NamedVariant{{G, S, W, P, D, 0, big_table(G, S), G == 64 && D == 1}, "msv_g" #G "_s" #S "_w" #W "_p" #P "_d" #D}
+#define MSV_SPLIT_VARIANT(G, S, SA, W, P) \
+    NamedVariant{{G, S, W, P, 1, SA, false, G == 64}, "msv_g" #G "_s" #S "_a" #SA "_w" #W "_p" #P "_d1"}
+#define MSV_COOP_VARIANT(W, S) NamedCoop{{W, S, (16 + S - 1) / S * S, S, true}, "msv_coop_w" #W "_s" #S}
+#define MSV_COOP_SPLIT_VARIANT(W, S, SA) \
+    NamedCoop{{W, S, (16 + S - 1) / S * S, SA, true}, "msv_coop_w" #W "_s" #S "_a" #SA}
+static const NamedVariant kVariants[] = {
+#include "msv_variants_0.inc"
+#include "msv_variants_1.inc"
+#include "msv_variants_2.inc"
+#include "msv_variants_3.inc"
+#include "msv_variants_4.inc"
+#include "msv_variants_5.inc"
+#include "msv_variants_6.inc"
+#include "msv_variants_7.inc"
+};
+static const NamedCoop kCoopVariants[] = {
+#include "msv_coop_variants.inc"
+};
+
+static msvplan::Tables plan_tables() {
+    msvplan::Tables t;
+    for (const NamedVariant& v : kVariants) t.variants.push_back(v.shape);
+    for (const NamedCoop& c : kCoopVariants) t.coop.push_back(c.shape);
+    return t;
+}
+
+static int variant_index(const std::string& name) {
+    for (size_t i = 0; i < sizeof(kVariants) / sizeof(kVariants[0]); ++i)
+        if (name == kVariants[i].name) return static_cast<int>(i);
+    return -1;
+}
+
+static std::string plan_name(const msvplan::PlanSet& ps, msvplan::Kind kind) {
+    const int i = kind == msvplan::kCoop ? ps.coop : kind == msvplan::kLatency ? ps.lat : kind == msvplan::kMid ? ps.mid : ps.main;
+    if (i < 0) return "";
+    return kind == msvplan::kCoop ? kCoopVariants[i].name : kVariants[i].name;
+}
+
+// A JSON value of tests/golden/msv_plans.json: objects, arrays, strings without escapes, unsigned integers.
+struct Json {
+    std::map<std::string, Json> object;
+    std::vector<Json> array;
+    std::string string;
+    uint64_t number = 0;
+    const Json& operator[](const char* key) const {
+        static const Json none;
+        const auto it = object.find(key);
+        return it == object.end() ? none : it->second;
+    }
+};
+
+static bool parse_json(const std::string& text, size_t& at, Json& out) {
+    auto skip = [&] {
+        while (at < text.size() && std::strchr(" \t\r\n,:", text[at])) ++at;
+    };
+    skip();
+    if (at >= text.size()) return false;
+    if (text[at] == '"') {
+        const size_t end = text.find('"', at + 1);
+        if (end == std::string::npos) return false;
+        out.string = text.substr(at + 1, end - at - 1);
+        at = end + 1;
+        return true;
+    }
+    if (text[at] == '{' || text[at] == '[') {
+        const bool object = text[at++] == '{';
+        for (skip(); at < text.size() && text[at] != (object ? '}' : ']'); skip()) {
+            Json key, value;
+            if (object && (!parse_json(text, at, key) || key.string.empty())) return false;
+            if (!parse_json(text, at, value)) return false;
+            if (object) out.object[key.string] = value;
+            else out.array.push_back(value);
+        }
+        return at++ < text.size();
+    }
+    const size_t start = at;
+    while (at < text.size() && text[at] >= '0' && text[at] <= '9') out.number = out.number * 10 + (text[at++] - '0');
+    return at > start;
+}
+
+static const char* const kPlanKeys[4][3] = {{"variant", "blocks", ""},
+                                            {"latency_variant", "latency_blocks", "latency_max_n"},
+                                            {"mid_variant", "mid_blocks", "mid_max_n"},
+                                            {"coop_variant", "coop_blocks", "coop_max_n"}};
+
+// 9a. choose() and which() give every recorded profile its recorded plans, ranges and variant_for(n), with the
+// recorded CU count and grids; then every model length 1..4096 (4097: none) keeps the policy's invariants.
+static void check_recorded_plans(const std::string& root, const msvplan::Tables& tables) {
+    Json rec;
+    size_t at = 0;
+    const std::string text = slurp(root + "/tests/golden/msv_plans.json");
+    CHECK(parse_json(text, at, rec));
+    const int cus = static_cast<int>(rec["cus"].number);
+    CHECK(cus > 0 && rec["records"].array.size() >= 100);
+    std::map<std::string, int> recorded_blocks;  // a kernel's persistent grid on the recorded device
+    for (const Json& r : rec["records"].array)
+        for (const auto& keys : kPlanKeys)
+            if (!r["describe"][keys[0]].string.empty())
+                recorded_blocks[r["describe"][keys[0]].string] = static_cast<int>(r["describe"][keys[1]].number);
+    bool asked_mid = false;
+    const msvplan::BlocksOf blocks_of = [&](msvplan::Kind kind, int i) {
+        asked_mid |= kind == msvplan::kMid;
+        const auto it = recorded_blocks.find(kind == msvplan::kCoop ? kCoopVariants[i].name : kVariants[i].name);
+        return it == recorded_blocks.end() ? cus : it->second;  // unrecorded: one block per CU
+    };
+    size_t points = 0;
+    for (const Json& r : rec["records"].array) {
+        const uint32_t states = static_cast<uint32_t>(r["states"].number);
+        const std::string& forced = r["forced"].string;
+        CHECK(forced.empty() || variant_index(forced) >= 0);
+        const msvplan::PlanSet ps = msvplan::choose(tables, states, true, variant_index(forced), cus, blocks_of);
+        const Json& d = r["describe"];
+        const bool same = plan_name(ps, msvplan::kMain) == d["variant"].string &&
+                          plan_name(ps, msvplan::kLatency) == d["latency_variant"].string &&
+                          plan_name(ps, msvplan::kMid) == d["mid_variant"].string &&
+                          plan_name(ps, msvplan::kCoop) == d["coop_variant"].string &&
+                          ps.lat_max_n == d["latency_max_n"].number && ps.mid_max_n == d["mid_max_n"].number &&
+                          ps.coop_max_n == d["coop_max_n"].number;
+        if (!same)
+            std::printf("  %u states %s: chose %s / %s <= %llu / %s <= %llu / %s <= %llu\n", states, forced.c_str(),
+                        plan_name(ps, msvplan::kMain).c_str(), plan_name(ps, msvplan::kLatency).c_str(),
+                        static_cast<unsigned long long>(ps.lat_max_n), plan_name(ps, msvplan::kMid).c_str(),
+                        static_cast<unsigned long long>(ps.mid_max_n), plan_name(ps, msvplan::kCoop).c_str(),
+                        static_cast<unsigned long long>(ps.coop_max_n));
+        CHECK(same);
+        CHECK(r["variant_for"].array.size() >= 3);
+        for (const Json& point : r["variant_for"].array) {
+            CHECK(point.array.size() == 2);
+            if (point.array.size() != 2) continue;
+            const uint64_t n = point.array[0].number;
+            const std::string got = plan_name(ps, msvplan::which(ps, n, true, false));
+            if (got != point.array[1].string)
+                std::printf("  %u states %s, n = %llu: %s, recorded %s\n", states, forced.c_str(),
+                            static_cast<unsigned long long>(n), got.c_str(), point.array[1].string.c_str());
+            CHECK(got == point.array[1].string);
+            CHECK(msvplan::which(ps, n, false, false) == msvplan::kMain);
+            ++points;
+        }
+    }
+    for (uint32_t states = 1; states <= 4096; ++states)
+        for (bool same_EJ : {true, false}) {
+            const msvplan::PlanSet ps = msvplan::choose(tables, states, same_EJ, -1, cus, blocks_of);
+            CHECK(ps.main >= 0);
+            if (ps.main < 0) continue;
+            for (int i : {ps.main, ps.lat, ps.mid})
+                CHECK(i < 0 || static_cast<uint32_t>(tables.variants[i].states()) >= states);
+            int smallest = -1;  // the covering cooperative variant of the fewest states
+            for (size_t i = 0; i < tables.coop.size(); ++i)
+                if (static_cast<uint32_t>(tables.coop[i].states()) >= states &&
+                    (smallest < 0 || tables.coop[i].states() < tables.coop[smallest].states()))
+                    smallest = static_cast<int>(i);
+            CHECK(ps.coop == (same_EJ ? smallest : -1));
+            CHECK((ps.coop >= 0) == (ps.coop_max_n > 0));
+            CHECK(ps.lat < 0 || ps.mid < 0 || ps.lat_max_n <= ps.mid_max_n);
+            CHECK(states >= 80 || tables.variants[ps.main].G >= 16);
+        }
+    CHECK(msvplan::choose(tables, 4097, true, -1, cus, blocks_of).main == -1);
+    CHECK(!asked_mid);
+    std::printf("  plan policy: %zu recorded profiles and %zu variant_for points on %d CUs; 1..4096 states swept\n",
+                rec["records"].array.size(), points, cus);
+}
+
+// 9b. the fused-grid decision, from the rules in msv_plan.cpp's comments
+static void check_fused_grid(const msvplan::Tables& tables) {
+    using msvplan::GridChoice;
+    using msvplan::GridProfile;
+    const int coop1400 = 2, lat1400 = variant_index("msv_g64_s24_w16_p6_d1");  // 1464 and 1536 states
+    CHECK(tables.coop[coop1400].states() == 1464 && lat1400 >= 0);
+    const GridProfile p{1400, false, true, 512};
+    auto run = [&](std::vector<GridProfile> g, uint64_t n, bool host_residues = false, uint32_t most = 1) {
+        return msvplan::fused_grid(tables, g.data(), static_cast<uint32_t>(g.size()), n, host_residues, most);
+    };
+    auto is = [](GridChoice c, int kind, int index) { return c.kind == kind && c.index == index; };
+    const GridProfile small{100, false, true, 384}, forced{1400, true, true, 0}, other_EJ{1400, false, false, 0},
+        no_coop{1400, false, true, 0};
+    CHECK(is(run({p, small, p}, 3), GridChoice::kCoopFused, coop1400));  // the layout of the largest model
+    CHECK(is(run({p}, 3), GridChoice::kPerProfile, -1));                 // a single profile
+    // n x profiles at 2048 and 2049 (above every cooperative range)
+    CHECK(is(run({p, p}, 1024), GridChoice::kLatencyFused, lat1400));
+    CHECK(is(run({p, p, p}, 683), GridChoice::kPerProfile, -1));
+    CHECK(is(run({p, forced, p}, 3), GridChoice::kPerProfile, -1));
+    CHECK(is(run({p, other_EJ, p}, 3), GridChoice::kLatencyFused, lat1400));
+    // workgroups of a launch at and one above the smallest coop_max_n
+    CHECK(is(run({p, small, p}, 128), GridChoice::kCoopFused, coop1400));
+    CHECK(is(run({p, small, p}, 129), GridChoice::kLatencyFused, lat1400));
+    CHECK(is(run(std::vector<GridProfile>(40, small), 12), GridChoice::kCoopFused, 0));  // 32 profiles per launch
+    CHECK(is(run(std::vector<GridProfile>(40, small), 13), GridChoice::kLatencyFused, variant_index("msv_g64_s4_w16_p1_d1")));
+    CHECK(is(run({p, no_coop}, 3), GridChoice::kLatencyFused, lat1400));
+    CHECK(is(run({p, p}, 3, true), GridChoice::kLatencyFused, lat1400));  // residues read in place
+    // a handle listed 8 and 9 times: the latency layout holds a counter slot per entry, the cooperative none
+    CHECK(is(run(std::vector<GridProfile>(9, no_coop), 3, false, 8), GridChoice::kLatencyFused, lat1400));
+    CHECK(is(run(std::vector<GridProfile>(9, no_coop), 3, false, 9), GridChoice::kPerProfile, -1));
+    CHECK(is(run(std::vector<GridProfile>(9, p), 3, false, 9), GridChoice::kCoopFused, coop1400));
+    CHECK(is(run({GridProfile{4096, false, true, 0}, p}, 3), GridChoice::kLatencyFused, variant_index("msv_g64_s64_w12_p2_d1")));
+}
+
+// 9c. plan_pieces: the cuts of the function as it stood in msv_device.cpp (printed by a scratch build of it),
+// and its properties on those and on random CSRs
+struct PieceCase {
+    const char* name;
+    uint32_t first_den, growth;
+    std::vector<uint64_t> offsets, cuts;
+};
+
+static std::vector<uint64_t> csr(uint64_t base, std::initializer_list<std::pair<uint64_t, uint64_t>> runs) {
+    std::vector<uint64_t> o{base};  // runs of (count, length)
+    for (const auto& r : runs)
+        for (uint64_t i = 0; i < r.first; ++i) o.push_back(o.back() + r.second);
+    return o;
+}
+
+static std::vector<uint64_t> checked_pieces(const std::vector<uint64_t>& offsets, uint32_t first_den, uint32_t growth) {
+    const uint64_t n = offsets.size() - 1;
+    const std::vector<uint64_t> cut = msvplan::plan_pieces(offsets.data(), n, offsets[n] - offsets[0], first_den, growth);
+    bool ok = cut.size() >= 1 && cut.front() == 0 && cut.back() == n && (n == 0) == (cut.size() == 1);
+    for (size_t k = 0; ok && k + 1 < cut.size(); ++k)
+        ok = cut[k] < cut[k + 1] && cut[k + 1] <= n && offsets[cut[k + 1]] - offsets[cut[k]] < msvplan::kChunkBytes &&
+             cut[k + 1] - cut[k] <= msvplan::kMaxLaunchSeqs - 1;
+    CHECK(ok);
+    return cut;
+}
+
+static void check_plan_pieces() {
+    const PieceCase cases[] = {
+        {"below 4 MiB", 4, 2, csr(0, {{1000, 1000}}), {0, 1000}},
+        {"8 MiB, remainder joins", 4, 2, csr(0, {{8192, 1024}}), {0, 2048, 8192}},
+        {"8 MiB, first_den 0", 0, 2, csr(0, {{8192, 1024}}), {0, 8192}},
+        {"8 MiB, growth 1, remainder stays", 4, 1, csr(0, {{8192, 1024}}), {0, 2048, 4096, 6144, 8192}},
+        {"9000 x 1024, growth 1", 4, 1, csr(0, {{9000, 1024}}), {0, 2250, 4500, 6750, 9000}},
+        {"a sequence longer than the first piece", 4, 2, csr(0, {{1, 5u << 20}, {3000, 1024}}), {0, 1, 3001}},
+        {"empty sequences around and inside", 4, 2,
+         csr(0, {{2000, 0}, {3000, 1000}, {500, 0}, {3000, 1000}, {2000, 0}}), {0, 3500, 10500}},
+        {"all empty", 4, 2, csr(0, {{5, 0}}), {0, 5}},
+        {"offsets from 12345", 4, 2, csr(12345, {{40000, 1000}}), {0, 10000, 40000}},
+        {"first_den 8", 8, 2, csr(0, {{40000, 1000}}), {0, 5000, 15000, 40000}},
+        {"growth 3", 8, 3, csr(7, {{40000, 1000}}), {0, 5000, 20000, 40000}},
+        {"one sequence of 6 MiB", 4, 2, csr(0, {{1, 6u << 20}}), {0, 1}},
+        {"10 GB: the chunk limit", 4, 2, csr(0, {{100000, 102400}}), {0, 25000, 66932, 100000}},
+    };
+    for (const PieceCase& c : cases) {
+        const bool same = checked_pieces(c.offsets, c.first_den, c.growth) == c.cuts;
+        if (!same) std::printf("  plan_pieces: %s\n", c.name);
+        CHECK(same);
+    }
+    CHECK(checked_pieces({0}, 4, 2) == std::vector<uint64_t>{0});  // no sequences
+    std::mt19937_64 rng(23);
+    for (int k = 0; k < 200; ++k) {
+        const uint64_t n = 1 + rng() % 3000, scale = 1ull << (rng() % 23);  // up to ~12 GB
+        std::vector<uint64_t> o{rng() % 1000};
+        for (uint64_t i = 0; i < n; ++i) o.push_back(o.back() + (rng() % 4 ? rng() % (2 * scale) : 0));
+        checked_pieces(o, static_cast<uint32_t>(rng() % 9), static_cast<uint32_t>(1 + rng() % 3));
+    }
+}
+
+static void check_plan_policy(const std::string& root) {
+    const msvplan::Tables tables = plan_tables();
+    CHECK(tables.variants.size() >= 80 && tables.coop.size() == 5);
+    check_recorded_plans(root, tables);
+    check_fused_grid(tables);
+    check_plan_pieces();
+}
+
 int main(int argc, char** argv) {
     const std::string root = argc > 1 ? argv[1] : ".";
     char tmpl[] = "/tmp/msv_sanitize_XXXXXX";
@@ -440,6 +721,9 @@ int main(int argc, char** argv) {
     // 8. the kernel-layout table builders (table_layout.cpp) on compiled geometries, at R = capacity,
     // capacity - 1 and 1 real states
     check_layouts();
+
+    // 9. the MSV plan policy (msv_plan.cpp): recorded plans, the fused-grid decision, the pipeline pieces
+    check_plan_policy(root);
 
     rmdir(dir.c_str());
     if (failures) {

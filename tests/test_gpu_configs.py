@@ -338,6 +338,46 @@ def test_describe_reports_every_plan():
     e.close()
 
 
+def test_plans_match_the_recording(tmp_path):
+    """The plans of this device's profiles are the recorded ones (tests/golden/msv_plans.json, written by
+    tools/record_msv_plans.py; the CPU driver tests/cpp/sanitize_host.cpp replays the policy against the same
+    file): describe() and variant_for(n) at every recorded n, for the 24 data profiles, every recorded length
+    whose plans differ from the previous recorded length's, and the three forced variants."""
+    import json
+    import torch
+    from hmm_fasta_viterbi_amd.synthetic import write_hmm
+    from oracle_lib import GOLD
+    with open(os.path.join(GOLD, "msv_plans.json")) as f:
+        rec = json.load(f)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert cus == rec["cus"], f"the plans were recorded on a device of {rec['cus']} CUs, this one has {cus}"
+
+    def plans(r):
+        return tuple(r["describe"][k] for k in ("variant", "latency_variant", "latency_max_n", "mid_variant",
+                                                 "mid_max_n", "coop_variant", "coop_max_n"))
+
+    auto = sorted((r for r in rec["records"] if not r["forced"]), key=lambda r: r["states"])
+    cases = [r for k, r in enumerate(auto)
+             if r["source"] != "synthetic" or k == 0 or plans(r) != plans(auto[k - 1])]
+    cases += [r for r in rec["records"] if r["forced"]]
+    assert sum(r["source"] != "synthetic" for r in cases) == 24 + 3 and len(cases) >= 60
+    for r in cases:
+        if r["source"] == "synthetic":
+            path = str(tmp_path / f"syn{r['states']}.hmm")
+            write_hmm(path, r["states"], 9000 + r["states"])
+        else:
+            path = profile_path(r["source"])
+        e = msv.MSV_HMM(msv.Profile_HMM(path))
+        try:
+            if r["forced"]:
+                e.set_variant(r["forced"])
+            assert e.describe() == r["describe"], (r["source"], r["states"], r["forced"])
+            for n, name in r["variant_for"]:
+                assert e.variant_for(n) == name, (r["source"], r["states"], r["forced"], n)
+        finally:
+            e.close()
+
+
 def test_async_stream_of_batches():
     """msv_score_batch_async / msv_profile_wait: three calls in flight (the copies of the later ones
     under the kernel of the first), results equal to the synchronous path; a bad residue is reported

@@ -29,7 +29,7 @@ from state_batches import boundary_batch, knock_out, numpy_msv, tail_homolog_bat
 
 MAX_STATES = 4096  # the largest model the compiled family covers (test_gpu_model_lengths.py)
 
-# The cooperative variants (msv_coop.hip kCoop): name -> (waves, S, halo, SA); states() = waves * (64 S - halo).
+# The cooperative variants (msv_coop_variants.inc): name -> (waves, S, halo, SA); states() = waves * (64 S - halo).
 # Pinned here: the tests below observe each capacity as the change of describe()'s coop_variant across it.
 COOP = {
     "msv_coop_w4_s2": (4, 2, 16, 2),
@@ -336,7 +336,7 @@ def test_score_grid_over_exact_fit_profiles(lengs, tmp_path_factory):
     try:
         infos = [e.describe() for e in engines]
         if max(lengs) <= max(COOP_STATES.values()):
-            # the rule of the fused cooperative launch (msv_device.cpp fused_coop_variant)
+            # the rule of the fused cooperative launch (msv_plan.cpp fused_grid)
             assert all(i["coop_variant"] for i in infos) and len(engines) * n <= min(i["coop_max_n"] for i in infos)
         else:
             assert len(engines) * n <= 2048 and not infos[-1]["coop_variant"]
