@@ -1,7 +1,7 @@
 // hip_rt.h -- the host device layer's HIP plumbing, shared by msv_device.cpp, vit_device.cpp,
 // msv_multi.cpp and the host half of fasta_device.hip: the device guard, the status mapping and its
-// return-on-error macro, move-only owners of device buffers, pinned buffers, streams and events, and the
-// checks every host entry point opens with.
+// return-on-error macro, move-only owners of device buffers, pinned buffers, streams and events, the checks
+// every host entry point opens with, and the staging of one host batch (CsrStaging).
 //
 // The owners never switch devices and never synchronise on their own (the one exception is documented at
 // DeviceBuffer::replace_with): whoever destroys or shrinks one does so with its device current and with
@@ -75,13 +75,14 @@ inline msv_status csr_extent(const uint64_t* offsets, uint64_t n, uint64_t* maxL
     return MSV_OK;
 }
 
-// Owner of one hipMalloc allocation of `capacity()` elements.  Converts to the raw pointer.
-template <typename T>
-class DeviceBuffer {
+// Owner of one allocation of `capacity()` elements: device memory (hipMalloc) or, Pinned, page-locked host
+// memory (hipHostMalloc with the caller's flags).  Converts to the raw pointer.
+template <typename T, bool Pinned>
+class Buffer {
 public:
-    DeviceBuffer() = default;
-    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
-    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+    Buffer() = default;
+    Buffer(Buffer&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    Buffer& operator=(Buffer&& o) noexcept {
         if (this != &o) {
             reset();
             p_ = std::exchange(o.p_, nullptr);
@@ -89,32 +90,34 @@ public:
         }
         return *this;
     }
-    ~DeviceBuffer() { reset(); }
+    ~Buffer() { reset(); }
 
     T* get() const { return p_; }
     operator T*() const { return p_; }
     size_t capacity() const { return cap_; }
     void reset() {
-        if (p_) (void)hipFree(p_);
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
         p_ = nullptr;
         cap_ = 0;
     }
     // Room for n elements: nothing when they fit, else the allocation is freed and one of max(n, 1) made
     // (contents are not kept, no growth factor).
-    hipError_t reserve(size_t n) {
+    hipError_t reserve(size_t n, unsigned pinned_flags = hipHostMallocDefault) {
         if (p_ && n <= cap_) return hipSuccess;
         reset();
         n = std::max<size_t>(n, 1);
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T));
+        void** const out = reinterpret_cast<void**>(&p_);
+        const hipError_t e = Pinned ? hipHostMalloc(out, n * sizeof(T), pinned_flags) : hipMalloc(out, n * sizeof(T));
         if (e == hipSuccess) cap_ = n;
         else p_ = nullptr;
         return e;
     }
-    // Uploads host[0 .. n) into a NEW allocation and adopts it; on failure the old one is untouched.  The
-    // old allocation may still be read by a launch in flight on any stream, so, when there is one, the
-    // device is synchronised before it is freed (the holders' only synchronisation).
+    // Device buffers: uploads host[0 .. n) into a NEW allocation and adopts it; on failure the old one is
+    // untouched.  The old allocation may still be read by a launch in flight on any stream, so, when there is
+    // one, the device is synchronised before it is freed (the holders' only synchronisation).
     hipError_t replace_with(const T* host, size_t n) {
-        DeviceBuffer fresh;
+        static_assert(!Pinned, "replace_with uploads to the device");
+        Buffer fresh;
         hipError_t e = fresh.reserve(n);
         if (e == hipSuccess) e = hipMemcpy(fresh.p_, host, n * sizeof(T), hipMemcpyHostToDevice);
         if (e != hipSuccess) return e;
@@ -127,93 +130,38 @@ private:
     T* p_ = nullptr;
     size_t cap_ = 0;
 };
-
-// The same for page-locked host memory (hipHostMalloc with the caller's flags).
 template <typename T>
-class PinnedBuffer {
-public:
-    PinnedBuffer() = default;
-    PinnedBuffer(PinnedBuffer&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
-    PinnedBuffer& operator=(PinnedBuffer&& o) noexcept {
-        if (this != &o) {
-            reset();
-            p_ = std::exchange(o.p_, nullptr);
-            cap_ = std::exchange(o.cap_, 0);
-        }
-        return *this;
-    }
-    ~PinnedBuffer() { reset(); }
-
-    T* get() const { return p_; }
-    operator T*() const { return p_; }
-    size_t capacity() const { return cap_; }
-    void reset() {
-        if (p_) (void)hipHostFree(p_);
-        p_ = nullptr;
-        cap_ = 0;
-    }
-    hipError_t reserve(size_t n, unsigned flags) {
-        if (p_ && n <= cap_) return hipSuccess;
-        reset();
-        n = std::max<size_t>(n, 1);
-        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T), flags);
-        if (e == hipSuccess) cap_ = n;
-        else p_ = nullptr;
-        return e;
-    }
-
-private:
-    T* p_ = nullptr;
-    size_t cap_ = 0;
-};
+using DeviceBuffer = Buffer<T, false>;
+template <typename T>
+using PinnedBuffer = Buffer<T, true>;
 
 // Owners of a stream and of an event, created on demand (create is a no-op once created).  Both convert
 // to the raw handle.
-class Stream {
+template <typename H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+class Handle {
 public:
-    Stream() = default;
-    Stream(Stream&& o) noexcept : s_(std::exchange(o.s_, nullptr)) {}
-    Stream& operator=(Stream&& o) noexcept {
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    Handle& operator=(Handle&& o) noexcept {
         if (this != &o) {
             reset();
-            s_ = std::exchange(o.s_, nullptr);
+            h_ = std::exchange(o.h_, nullptr);
         }
         return *this;
     }
-    ~Stream() { reset(); }
-    hipError_t create(unsigned flags) { return s_ ? hipSuccess : hipStreamCreateWithFlags(&s_, flags); }
-    operator hipStream_t() const { return s_; }
+    ~Handle() { reset(); }
+    hipError_t create(unsigned flags) { return h_ ? hipSuccess : Create(&h_, flags); }
+    operator H() const { return h_; }
     void reset() {
-        if (s_) (void)hipStreamDestroy(s_);
-        s_ = nullptr;
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
     }
 
 private:
-    hipStream_t s_ = nullptr;
+    H h_ = nullptr;
 };
-
-class Event {
-public:
-    Event() = default;
-    Event(Event&& o) noexcept : e_(std::exchange(o.e_, nullptr)) {}
-    Event& operator=(Event&& o) noexcept {
-        if (this != &o) {
-            reset();
-            e_ = std::exchange(o.e_, nullptr);
-        }
-        return *this;
-    }
-    ~Event() { reset(); }
-    hipError_t create(unsigned flags) { return e_ ? hipSuccess : hipEventCreateWithFlags(&e_, flags); }
-    operator hipEvent_t() const { return e_; }
-    void reset() {
-        if (e_) (void)hipEventDestroy(e_);
-        e_ = nullptr;
-    }
-
-private:
-    hipEvent_t e_ = nullptr;
-};
+using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
 
 // Synchronises up to three streams when a host call returns early: copies that read its pinned staging
 // (rewritten by the next call) and kernels that write its buffers may still be queued.  disarm() on the
@@ -258,5 +206,51 @@ T* mapped_host(T* host) {
     }
     return static_cast<T*>(d);
 }
+
+// One staged host batch: the device residues, offsets, dequeue order and scores, and the pinned host copy of
+// the rebased offsets (a true async DMA; rewritten by the next upload, so whoever uploads lets the stream
+// finish first: a StreamDrain on early returns).  Never switches devices, never synchronises.
+struct CsrStaging {
+    DeviceBuffer<uint8_t> d_res;
+    DeviceBuffer<uint64_t> d_off;
+    DeviceBuffer<uint32_t> d_order;
+    DeviceBuffer<float> d_scores;
+    PinnedBuffer<uint64_t> h_off;
+
+    // Room for `words` offset words (device and h_off) and `bytes` residue bytes.  THE rule for batches without
+    // residues: d_res always holds a readable byte (reserve never allocates less), since for an empty sequence
+    // a kernel computes one discarded row on byte 0.  readable(): the residues a launch over `bytes` reads.
+    hipError_t reserve_inputs(uint64_t words, uint64_t bytes) {
+        hipError_t e = d_res.reserve(bytes);
+        if (e == hipSuccess) e = d_off.reserve(words);
+        return e == hipSuccess ? h_off.reserve(words) : e;
+    }
+    const uint8_t* readable(const uint8_t* src, uint64_t bytes) const { return bytes ? src : d_res.get(); }
+    // Room for the dequeue order of n sequences and for `scores` scores (0: they are written elsewhere).
+    hipError_t reserve_results(uint64_t n, uint64_t scores) {
+        const hipError_t e = d_order.reserve(n);
+        return e == hipSuccess && scores ? d_scores.reserve(scores) : e;
+    }
+    // Stages sequences [first, last) of a host CSR as one batch (none: `offsets` may be null): reserves the
+    // inputs, rebases the offsets into h_off, queues their H2D on `off_stream` and, if copy_residues (they
+    // are not read in place) and there are any, the residues' on `res_stream`.  On one stream the residues go
+    // first (msv_score_grid's 24 x 3 grid of pageable residues: 0.44 ms, against 0.46 ms behind the offsets'
+    // copy); on two the offsets, which the order kernel waits for.
+    hipError_t upload(const uint8_t* residues, const uint64_t* offsets, uint64_t first, uint64_t last,
+                      bool copy_residues, hipStream_t off_stream, hipStream_t res_stream) {
+        const uint64_t n = last - first, bytes = n && copy_residues ? offsets[last] - offsets[first] : 0;
+        hipError_t e = reserve_inputs(n + 1, bytes);
+        if (e != hipSuccess) return e;
+        if (n) msvplan::rebase_offsets(offsets, first, last, h_off);
+        else h_off[0] = 0;
+        const auto copy_res = [&] {
+            return bytes ? hipMemcpyAsync(d_res, residues + offsets[first], bytes, hipMemcpyHostToDevice, res_stream)
+                         : hipSuccess;
+        };
+        if (off_stream == res_stream && (e = copy_res()) != hipSuccess) return e;
+        e = hipMemcpyAsync(d_off, h_off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, off_stream);
+        return e == hipSuccess && off_stream != res_stream ? copy_res() : e;
+    }
+};
 
 }  // namespace msvrt

@@ -26,10 +26,10 @@
 #include "msv_kernel.h"
 #include "msv_plan.h"
 
+using msvplan::CallPlan;
 using msvplan::kLaunchSlots;
-using msvplan::kPipelineMin;
-using msvplan::plan_pieces;
 using msvrt::csr_extent;
+using msvrt::CsrStaging;
 using msvrt::DeviceBuffer;
 using msvrt::DeviceGuard;
 using msvrt::hip_status;
@@ -37,6 +37,7 @@ using msvrt::kChunkBytes;
 using msvrt::kMaxLaunchSeqs;
 using msvrt::mapped_host;
 using msvrt::PinnedBuffer;
+using msvrt::StreamDrain;
 
 // table_layout.cpp builds the tables without msv_kernel.h
 static_assert(msvk::kAminoAcids == 20 && msvk::kPoisonRow == 20 && msvk::kTableRows == 21, "table_layout.cpp's rows");
@@ -57,14 +58,6 @@ constexpr int kAsyncSlots = 3;
 constexpr int kErrWord = 2 * kLaunchSlots;
 constexpr int kHostErrWord = kErrWord + 1 + kAsyncSlots;
 constexpr int kWords = kHostErrWord + 1;
-// Small host calls (pageable residues of at most kSmallCall bytes, at most kSmallCall sequences -- the
-// reference's one-sequence-per-call pattern): residues staged behind the offsets in the pinned offsets
-// buffer and sent in ONE H2D; pageable scores written by the kernel into pinned staging (no D2H).
-constexpr uint64_t kSmallCall = 1ull << 20;
-// Page-locked residues are read in place unless the model has fewer than kInPlaceMinStates states and the
-// batch at least kInPlaceAnyBytes residues (msv_score_batch).
-constexpr uint32_t kInPlaceMinStates = 300;
-constexpr uint64_t kInPlaceAnyBytes = 16ull << 20;
 
 // MSV_HMM::init_transitions_depend_on_seq (MSV_HMM.cpp:59-64) for every length < n, with the
 // host's logf (never a device logf, so the per-sequence constants are the reference's bits).
@@ -135,16 +128,16 @@ struct msv_profile {
     uint32_t lentab_n = 0;
     DeviceBuffer<uint32_t> d_words;  // kLaunchSlots x {dequeue counter, waves still running}, sticky error bits
     DeviceBuffer<uint32_t> d_hist;  // kLaunchSlots longest-first counting-sort scratches [hist | cursors]
-    DeviceBuffer<uint8_t> d_dummy;  // a readable residue byte for batches with no residues
+    DeviceBuffer<uint8_t> d_dummy;  // device API: a readable residue byte for launches given no residues
     LaunchRing kernels, orders;   // launch slots of the MSV kernel and of the order sort
     msvrt::Stream stream;
     hipStream_t bound = nullptr;  // msv_profile_bind_stream: a caller stream guaranteed alive while bound
-    // host-API pipeline (msv_score_batch): a second compute stream, a copy stream, piece events,
-    // and pinned staging for the rebased offsets
+    // host-API pipeline (msv_score_batch): a second compute stream, a copy stream and piece events
     msvrt::Stream stream2, copy_stream;
     msvrt::Stream offsets_stream;  // msv_score_batch_async: the offsets' H2D, beside the residues'
     std::vector<msvrt::Event> events;
-    PinnedBuffer<uint64_t> h_off;
+    // host-API staging (msv_score_batch, msv_score_grid; msv_score_fasta_device's order and scores)
+    CsrStaging host;
     PinnedBuffer<float> h_sc;  // pinned score staging of small calls with pageable destinations
     uint32_t pipe_first_den = 4, pipe_growth = 2;  // piece sizes: total / first_den, then x growth
     uint32_t pipe_streams = 2;                      // compute streams the pieces alternate over
@@ -153,11 +146,7 @@ struct msv_profile {
     // msv_score_batch_async: kAsyncSlots staging sets, so the H2D of one call runs under the kernel
     // of the call before it
     struct AsyncSlot {
-        DeviceBuffer<uint8_t> d_res;
-        DeviceBuffer<uint64_t> d_off;
-        DeviceBuffer<float> d_sc;
-        DeviceBuffer<uint32_t> d_ord;
-        PinnedBuffer<uint64_t> h_off;  // pinned rebased offsets
+        CsrStaging staged;
         PinnedBuffer<uint32_t> h_err;  // pinned copy of the slot's error word
         const float* direct = nullptr;  // page-locked destination written by the kernel (errors: scan)
         uint64_t n = 0;
@@ -166,11 +155,6 @@ struct msv_profile {
         bool pending = false;
     } async[kAsyncSlots];
     uint64_t next_ticket = 1;
-    // host-API staging
-    DeviceBuffer<uint8_t> d_res;
-    DeviceBuffer<uint64_t> d_off;
-    DeviceBuffer<float> d_scores;
-    DeviceBuffer<uint32_t> d_order;  // msv_score_fasta_device's longest-first order
     uint64_t* d_stamps = nullptr;  // diagnostic timeline buffer (tools only), or nullptr
     bool stamp_clock = false;      // d_stamps is for the CLOCK twins (kStampWords per wave: bench.py clock_GHz)
     hipEvent_t time_start = nullptr, time_stop = nullptr;  // msv_debug_time_next_launch (one launch)
@@ -607,12 +591,6 @@ msv_status msv_score_batch_device(msv_profile* p, const uint8_t* d_residues, uin
     return launch_batch(p, d_residues, residues_len, d_offsets, n, d_order, d_scores, stream, true);
 }
 
-// Library-internal (msv_score_batch, msv_multi.cpp): whether page-locked residues of `bytes` bytes are read
-// in place (zero-copy) rather than copied -- see msv_score_batch.
-__attribute__((visibility("hidden"))) bool msv_in_place_wins(const msv_profile* p, uint64_t bytes) {
-    return p->model_length - 1 >= kInPlaceMinStates || bytes < kInPlaceAnyBytes;
-}
-
 // Library-internal (msv_multi.cpp): msv_score_batch_device for residues that are the device alias of
 // page-locked host memory -- the launch takes the variant's zero-copy twin (msv_kernel.hip zc_fn).
 __attribute__((visibility("hidden"))) msv_status msv_score_batch_host_residues(
@@ -643,6 +621,21 @@ static msv_status check_word(msv_profile* p, hipStream_t st, int word) {
     if (err) MSV_HIP(hipMemsetAsync(p->d_words + word, 0, sizeof(uint32_t), st));
     MSV_HIP(hipStreamSynchronize(st));
     return err_status(err);
+}
+
+// The status of a finished batch whose `n` scores are on the host, with `st` idle.  Every error leaves a score
+// that is +inf or NaN (scan_scores), so the latched error words are read back only on that rare path (a 4-byte
+// read-back is a blit launch plus a synchronisation: 4 us per call, 0.9 ms over a grid's 24 profiles, more
+// than its kernels): then word `word` of EVERY listed profile is read and cleared, the first status reported.
+static msv_status host_scores_status(const float* scores, uint64_t n, msv_profile* const* profiles, uint32_t n_profiles,
+                                     hipStream_t st, int word) {
+    if (scan_scores(scores, n) == MSV_OK) return MSV_OK;
+    msv_status first = MSV_OK;
+    for (uint32_t i = 0; i < n_profiles; ++i) {
+        const msv_status s = check_word(profiles[i], st, word);
+        if (first == MSV_OK) first = s;
+    }
+    return first != MSV_OK ? first : scan_scores(scores, n);
 }
 
 msv_status msv_profile_check(msv_profile* p, void* stream) {
@@ -685,9 +678,9 @@ msv_status msv_host_free(void* ptr) {
 
 msv_status msv_score_batch(msv_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
                            float* scores, void* stream) {
+    // 1. validate: the CSR on the host (cheap, O(n)), and find the longest sequence
     if (!p || (n && (!offsets || !scores))) return MSV_ERR_INVALID_ARGUMENT;
     if (n == 0) return MSV_OK;
-    // Validate the CSR on the host (cheap, O(n)) and find the longest sequence.
     uint64_t maxL = 0, total = 0;
     msv_status s = csr_extent(offsets, n, &maxL, &total);
     if (s != MSV_OK) return s;
@@ -700,38 +693,34 @@ msv_status msv_score_batch(msv_profile* p, const uint8_t* residues, const uint64
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : p->stream;
 
-    // Copy/compute pipeline.  The batch is cut into pieces (contiguous sequence ranges) whose
-    // residue counts grow geometrically from 1/4 of the batch (x2: 2 pieces for cfg3, the best plan
-    // in tools/host_pipeline_sweep.py, profiles/r02_host_pipeline_sweep.jsonl), so the first kernel
-    // starts after a short copy and every later piece's H2D (copy stream) runs under the kernels of
-    // the pieces before it.  All offsets go first, and every piece's longest-first order runs before
-    // the first kernel (under piece 0's residue copy).  Pieces alternate between two compute
-    // streams, so a piece's kernel fills the CUs that the previous piece's drain tail frees (each
-    // launch has its own dequeue counter slot).  Scores and the error word come back once at the end
-    // (pageable destinations would make per-piece D2H copies block the host thread that enqueues the
-    // pipeline), followed by ONE synchronisation.
-    // Page-locked residues are not copied at all: the kernel reads them in place over PCIe through their
-    // device alias (zero-copy; L2 keeps each 128-B line for the rows that follow).  cfg3: kernel 2.98 vs
+    // 2. plan (msv_plan.h plan_call): how the residues reach the kernels, the pieces, the staging layout.
+    // IN PLACE.  Page-locked residues are not copied at all: the kernel reads them in place over PCIe through
+    // their device alias (zero-copy; L2 keeps each 128-B line for the rows that follow).  cfg3: kernel 2.98 vs
     // 2.87 ms from HBM -- 0.96 of the resident rate with no copy, against ~0.85 for the copy pipeline
     // below, whose first piece's copy and extra drain tail it saves (profiles/r02_zero_copy_probe.jsonl).
     // One launch per < 2^32-byte piece; no copy stream, no second compute stream.
-    // Except for large batches of small models, whose kernel consumes residues faster than the ~25 GB/s at
-    // which a kernel reads host memory: page-locked 100k x U[300,500] batches, per call in place vs copied
-    // (profiles/r03_ab_in_place_vs_copied.jsonl): 100.hmm 1.60 vs 1.24 ms, 200.hmm 1.69 vs 1.46, 400.hmm
+    // Except for large batches of small models (in_place_wins), whose kernel consumes residues faster than the
+    // ~25 GB/s at which a kernel reads host memory: page-locked 100k x U[300,500] batches, per call in place vs
+    // copied (profiles/r03_ab_in_place_vs_copied.jsonl): 100.hmm 1.60 vs 1.24 ms, 200.hmm 1.69 vs 1.46, 400.hmm
     // 1.68 vs 1.76, 600.hmm 1.75 vs 2.33, 1400.hmm 3.09 vs 3.36; 100.hmm x 20k (8 MB) 0.41 vs 0.44.
-    const bool in_place_wins = msv_in_place_wins(p, total);
-    const uint8_t* const zres = (total && p->zero_copy && in_place_wins) ? mapped_host(residues) : nullptr;
-    const std::vector<uint64_t> cut = plan_pieces(offsets, n, total, zres ? 0 : p->pipe_first_den, p->pipe_growth);
-    const size_t P = cut.size() - 1;
     // SMALL calls: the residues ride in the offsets' H2D (behind the n + 1 offsets, in u64 words), and
     // pageable scores are written by the kernel into pinned staging.  A one-sequence call was two H2D
     // and two D2H blits, the scores' D2H to pageable memory a ~25 us round trip on the host
     // (profiles/r03_reference_call_timeline.txt).
-    const bool small = !zres && total <= kSmallCall && n <= kSmallCall;
-    const uint64_t res_words = small ? (total + 7) / 8 : 0;
-    if (!zres && !small) MSV_HIP(p->d_res.reserve(std::max<uint64_t>(total, 1)));
-    MSV_HIP(p->d_off.reserve(n + P + res_words));
-    // a page-locked destination is written by the kernels themselves (no D2H of the scores)
+    // COPIED, as a copy/compute pipeline from kPipelineMin residues up.  The batch is cut into pieces
+    // (contiguous sequence ranges) whose residue counts grow geometrically from 1/4 of the batch (x2: 2 pieces
+    // for cfg3, the best plan in tools/host_pipeline_sweep.py, profiles/r02_host_pipeline_sweep.jsonl), so the
+    // first kernel starts after a short copy and every later piece's H2D (copy stream) runs under the kernels
+    // of the pieces before it.
+    const uint8_t* const zres = (total && p->zero_copy && msvplan::in_place_wins(p->model_length - 1, total))
+                                    ? mapped_host(residues) : nullptr;
+    const CallPlan plan = msvplan::plan_call(offsets, n, total, zres != nullptr, p->pipe_first_den, p->pipe_growth);
+    const std::vector<uint64_t>& cut = plan.cut;
+    const size_t P = plan.pieces();
+    const bool in_place = plan.mode == CallPlan::kInPlace, small = plan.mode == CallPlan::kSmall, pipe = plan.pipeline;
+    // 3. reserve.  A page-locked destination is written by the kernels themselves (no D2H of the scores);
+    // the offsets' pinned staging also holds the small call's residues and the error word (plan's layout).
+    CsrStaging& sg = p->host;
     float* direct = mapped_host(scores);
     const bool staged_scores = !direct && small;
     if (staged_scores) {
@@ -739,14 +728,15 @@ msv_status msv_score_batch(msv_profile* p, const uint8_t* residues, const uint64
         direct = mapped_host(p->h_sc.get());
         if (!direct) return MSV_ERR_HIP;
     }
-    if (!direct) MSV_HIP(p->d_scores.reserve(n));
-    float* const dsc = direct ? direct : p->d_scores.get();
-    MSV_HIP(p->d_order.reserve(n));
-    // pinned: the offsets H2D is a true async DMA (+ the error word)
-    MSV_HIP(p->h_off.reserve(n + P + 8 + res_words, hipHostMallocDefault));
-    uint32_t* h_err = reinterpret_cast<uint32_t*>(p->h_off + n + P + res_words);
-    const uint8_t* const d_small_res = reinterpret_cast<const uint8_t*>(p->d_off + n + P);  // SMALL: residues
-    const bool pipe = P > 1 && !zres;
+    MSV_HIP(sg.reserve_inputs(plan.staged_words(), plan.mode == CallPlan::kCopied ? total : 0));
+    MSV_HIP(sg.reserve_results(n, direct ? 0 : n));
+    float* const dsc = direct ? direct : sg.d_scores.get();
+    uint32_t* const h_err = reinterpret_cast<uint32_t*>(sg.h_off + plan.err_word());
+    const uint8_t* const d_small_res = reinterpret_cast<const uint8_t*>(sg.d_off + plan.small_res_word());
+
+    // 4. fork: the pipeline's copy stream and second compute stream start after the caller's stream's
+    // earlier work.  On an early error return, copies reading the pinned h_off (rewritten by the next call)
+    // and kernels writing the staging buffers may still be queued: drain every stream used first.
     hipStream_t cs[2] = {st, st}, cp = st;
     if (pipe) {
         MSV_HIP(p->stream2.create(hipStreamNonBlocking));
@@ -754,80 +744,71 @@ msv_status msv_score_batch(msv_profile* p, const uint8_t* residues, const uint64
         cs[1] = p->pipe_streams == 2 ? p->stream2 : st;
         cp = p->copy_stream;
     }
-    // On an early error return, copies reading the pinned h_off (rewritten by the next call) and
-    // kernels writing the staging buffers may still be queued: drain every stream used first.
-    msvrt::StreamDrain drain(cs[0], cs[1], cp);
+    StreamDrain drain(cs[0], cs[1], cp);
     if (pipe) {
         while (p->events.size() < P + 4) {
             msvrt::Event e;
             MSV_HIP(e.create(hipEventDisableTiming | hipEventReleaseToDevice));
             p->events.push_back(std::move(e));
         }
-        // fork: both helper streams start after the caller's stream's earlier work
         MSV_HIP(hipEventRecord(p->events[P + 2], st));
         MSV_HIP(hipStreamWaitEvent(cp, p->events[P + 2], 0));
         MSV_HIP(hipStreamWaitEvent(cs[1], p->events[P + 2], 0));
     }
-    // 1. the residue pieces go first, in order, on the copy stream: their DMA is the critical path
-    const uint64_t base0 = offsets[0];
+    // 5. the residue pieces go first, in order, on the copy stream: their DMA is the critical path
     for (size_t k = 0; k < P; ++k) {
-        const uint64_t lo = offsets[cut[k]] - base0, bytes = offsets[cut[k + 1]] - offsets[cut[k]];
-        if (bytes && !zres && !small)
-            MSV_HIP(hipMemcpyAsync(p->d_res + lo, residues + base0 + lo, bytes, hipMemcpyHostToDevice, cp));
+        const uint64_t at = offsets[cut[k]], bytes = offsets[cut[k + 1]] - at;
+        if (bytes && plan.mode == CallPlan::kCopied)
+            MSV_HIP(hipMemcpyAsync(sg.d_res + (at - offsets[0]), residues + at, bytes, hipMemcpyHostToDevice, cp));
         if (pipe) MSV_HIP(hipEventRecord(p->events[2 + k], cp));  // piece k's residues landed
     }
-    // 2. meanwhile every piece's offsets (rebased on the piece's first residue, at h_off[cut[k] + k ..])
-    //    in ONE H2D on the caller's stream, then every piece's longest-first order there, under the
-    //    first residue copy (an order kernel enqueued behind a running MSV kernel would find no free
-    //    VGPRs until that kernel's blocks drain, delaying the next piece's launch)
-    for (size_t k = 0; k < P; ++k) {
-        uint64_t* ho = p->h_off + cut[k] + k;
-        const uint64_t base = offsets[cut[k]], cn = cut[k + 1] - cut[k];
-        for (uint64_t i = 0; i <= cn; ++i) ho[i] = offsets[cut[k] + i] - base;
-    }
-    if (small && total) std::memcpy(p->h_off + n + P, residues + base0, total);
-    MSV_HIP(hipMemcpyAsync(p->d_off, p->h_off, (n + P + res_words) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    const bool sort = pipe || !order_needless(p, n, zres != nullptr);
+    // 6. meanwhile every piece's offsets (rebased on the piece's first residue, at plan.offsets_word(k))
+    //    in ONE H2D on the caller's stream, then every piece's longest-first order there, before the first
+    //    kernel and under the first residue copy (an order kernel enqueued behind a running MSV kernel would
+    //    find no free VGPRs until that kernel's blocks drain, delaying the next piece's launch)
+    for (size_t k = 0; k < P; ++k) msvplan::rebase_offsets(offsets, cut[k], cut[k + 1], sg.h_off + plan.offsets_word(k));
+    if (small && total) std::memcpy(sg.h_off + plan.small_res_word(), residues + offsets[0], total);
+    MSV_HIP(hipMemcpyAsync(sg.d_off, sg.h_off, plan.upload_words() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    const bool sort = pipe || !order_needless(p, n, in_place);
     for (size_t k = 0; k < P && sort; ++k) {
-        s = msv_order_longest_first(p, p->d_off + cut[k] + k, cut[k + 1] - cut[k], p->d_order + cut[k], st);
+        s = msv_order_longest_first(p, sg.d_off + plan.offsets_word(k), cut[k + 1] - cut[k], sg.d_order + cut[k], st);
         if (s != MSV_OK) return s;
     }
     if (pipe) {
         MSV_HIP(hipEventRecord(p->events[1], st));  // offsets and orders done
         MSV_HIP(hipStreamWaitEvent(cs[1], p->events[1], 0));
     }
-    // 3. the kernels, alternating over the compute streams so that the LAST piece runs on the caller's
-    //    stream (the scores' D2H then waits on no other stream), each after its piece's residues
+    // 7. the kernels, each after its piece's residues.  Pieces alternate over the two compute streams, so a
+    //    piece's kernel fills the CUs that the previous piece's drain tail frees (each launch has its own
+    //    dequeue counter slot), and so that the LAST piece runs on the caller's stream (the scores' D2H then
+    //    waits on no other stream).
     for (size_t k = 0; k < P; ++k) {
-        const uint64_t lo = offsets[cut[k]] - base0, bytes = offsets[cut[k + 1]] - offsets[cut[k]];
+        const uint64_t at = offsets[cut[k]], bytes = offsets[cut[k + 1]] - at;
         hipStream_t c = cs[(P - 1 - k) & 1];
         if (pipe) MSV_HIP(hipStreamWaitEvent(c, p->events[2 + k], 0));
-        const uint8_t* src = zres ? zres + base0 + lo : (small ? d_small_res : p->d_res) + lo;
-        s = launch_batch(p, bytes ? src : p->d_dummy, std::max<uint64_t>(bytes, 1), p->d_off + cut[k] + k,
-                         cut[k + 1] - cut[k], sort ? p->d_order + cut[k] : nullptr, dsc + cut[k], c, !pipe,
-                         p->d_words + kHostErrWord, zres && bytes);
+        const uint8_t* src = in_place ? zres + at : (small ? d_small_res : sg.d_res.get()) + (at - offsets[0]);
+        s = launch_batch(p, sg.readable(src, bytes), std::max<uint64_t>(bytes, 1), sg.d_off + plan.offsets_word(k),
+                         cut[k + 1] - cut[k], sort ? sg.d_order + cut[k] : nullptr, dsc + cut[k], c, !pipe,
+                         p->d_words + kHostErrWord, in_place && bytes);
         if (s != MSV_OK) return s;
     }
-    if (pipe) {  // join the second compute stream (done before the last piece) back into the caller's
+    // 8. join the second compute stream (done before the last piece) back into the caller's
+    if (pipe) {
         MSV_HIP(hipEventRecord(p->events[P + 3], cs[1]));
         MSV_HIP(hipStreamWaitEvent(st, p->events[P + 3], 0));
     }
-    if (direct) {
-        // scores in page-locked memory: every error leaves a score that is +inf or NaN (scan_scores), so
-        // the error word is read only on that rare path (its D2H was a blit launch + 4 us per call)
-        MSV_HIP(hipStreamSynchronize(st));  // also: the pinned h_off is rewritten by the next call
-        drain.disarm();
-        if (staged_scores) std::memcpy(scores, p->h_sc, n * sizeof(float));
-        if (scan_scores(scores, n) == MSV_OK) return MSV_OK;
-        const msv_status e = check_word(p, st, kHostErrWord);  // reads, clears and reports this call's bits
-        return e != MSV_OK ? e : scan_scores(scores, n);
+    // 9. finish.  Scores and the error word come back once at the end (pageable destinations would make
+    //    per-piece D2H copies block the host thread that enqueues the pipeline), followed by ONE
+    //    synchronisation (also: the pinned h_off is rewritten by the next call).
+    if (!direct) {
+        MSV_HIP(hipMemcpyAsync(scores, sg.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        MSV_HIP(hipMemcpyAsync(h_err, p->d_words + kHostErrWord, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
-    MSV_HIP(hipMemcpyAsync(scores, p->d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    MSV_HIP(hipMemcpyAsync(h_err, p->d_words + kHostErrWord, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    MSV_HIP(hipStreamSynchronize(st));  // also: the pinned h_off is rewritten by the next call
+    MSV_HIP(hipStreamSynchronize(st));
     drain.disarm();
-    if (*h_err == 0) return MSV_OK;
-    return check_word(p, st, kHostErrWord);  // reads, clears and reports this call's error bits
+    if (!direct) return *h_err == 0 ? MSV_OK : check_word(p, st, kHostErrWord);  // reads, clears, reports its bits
+    if (staged_scores) std::memcpy(scores, p->h_sc, n * sizeof(float));
+    return host_scores_status(scores, n, &p, 1, st, kHostErrWord);  // (scores in page-locked memory)
 }
 
 msv_status msv_score_batch_async(msv_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
@@ -852,14 +833,9 @@ msv_status msv_score_batch_async(msv_profile* p, const uint8_t* residues, const 
     MSV_HIP(a.off_copied.create(hipEventDisableTiming));
     MSV_HIP(a.done.create(hipEventDisableTiming));
     MSV_HIP(a.h_err.reserve(64 / sizeof(uint32_t), hipHostMallocDefault));
-    MSV_HIP(a.d_res.reserve(std::max<uint64_t>(total, 1)));
-    MSV_HIP(a.d_off.reserve(n + 1));
+    CsrStaging& sg = a.staged;
     float* const direct = n ? mapped_host(scores) : nullptr;
-    if (!direct) MSV_HIP(a.d_sc.reserve(std::max<uint64_t>(n, 1)));
-    MSV_HIP(a.d_ord.reserve(std::max<uint64_t>(n, 1)));
-    MSV_HIP(a.h_off.reserve(n + 1, hipHostMallocDefault));
-    const uint64_t base = n ? offsets[0] : 0;
-    for (uint64_t i = 0; i <= n; ++i) a.h_off[i] = n ? offsets[i] - base : 0;
+    MSV_HIP(sg.reserve_results(n, direct ? 0 : std::max<uint64_t>(n, 1)));
     const int slot = static_cast<int>(&a - p->async);
     uint32_t* d_err = p->d_words + kErrWord + 1 + slot;
     // Consecutive calls alternate over two compute streams, so a call's kernel fills the CUs that the
@@ -869,31 +845,30 @@ msv_status msv_score_batch_async(msv_profile* p, const uint8_t* residues, const 
     hipStream_t cp = p->copy_stream, co = p->offsets_stream, cs = odd ? p->stream2 : p->stream;
     // On an error return after the first enqueue, copies reading this slot's pinned offsets (rewritten by
     // the slot's next call) may still be queued: drain the call's streams first.
-    msvrt::StreamDrain drain(co, cp, cs);
+    StreamDrain drain(co, cp, cs);
     // copy streams: this call's inputs (they overlap the earlier calls' kernels on the compute streams).
     // Nothing but copies goes on them: a kernel there (the order, as in round 2) waits for the running MSV
     // grid to drain before it can start, and every later call's copies queued behind it.  The offsets
     // have a stream of their own, so the copy stream carries the residues back to back (cfg2: 83 us
     // each, which set the call rate with the offsets' 8 us copy and the gaps between them in the same
     // stream -- profiles/r03_cfg2_streamed_timeline.txt) and the order starts once the offsets land.
-    MSV_HIP(hipMemcpyAsync(a.d_off, a.h_off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, co));
+    MSV_HIP(sg.upload(residues, offsets, 0, n, true, co, cp));
     MSV_HIP(hipEventRecord(a.off_copied, co));
-    if (total) MSV_HIP(hipMemcpyAsync(a.d_res, residues + base, total, hipMemcpyHostToDevice, cp));
     MSV_HIP(hipEventRecord(a.copied, cp));
     // compute stream: order, kernel, scores and the slot's error word back to the host (the order runs
     // in the previous call's drain tail: that call's kernel is on the other compute stream)
     MSV_HIP(hipStreamWaitEvent(cs, a.off_copied, 0));
     const bool sort = n && !order_needless(p, n, false);
     if (sort) {
-        s = msv_order_longest_first(p, a.d_off, n, a.d_ord, cs);
+        s = msv_order_longest_first(p, sg.d_off, n, sg.d_order, cs);
         if (s != MSV_OK) return s;
     }
     MSV_HIP(hipStreamWaitEvent(cs, a.copied, 0));
     if (n) {
-        s = launch_batch(p, total ? a.d_res : p->d_dummy, std::max<uint64_t>(total, 1), a.d_off, n,
-                         sort ? a.d_ord.get() : nullptr, direct ? direct : a.d_sc, cs, true, d_err);
+        s = launch_batch(p, sg.readable(sg.d_res, total), std::max<uint64_t>(total, 1), sg.d_off, n,
+                         sort ? sg.d_order.get() : nullptr, direct ? direct : sg.d_scores.get(), cs, true, d_err);
         if (s != MSV_OK) return s;
-        if (!direct) MSV_HIP(hipMemcpyAsync(scores, a.d_sc, n * sizeof(float), hipMemcpyDeviceToHost, cs));
+        if (!direct) MSV_HIP(hipMemcpyAsync(scores, sg.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, cs));
     }
     if (!direct) {  // (direct: errors are read from the scores; nothing else follows the kernel)
         MSV_HIP(hipMemcpyAsync(a.h_err, d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
@@ -917,18 +892,9 @@ msv_status msv_profile_wait(msv_profile* p, uint64_t ticket) {
         if (!g.ok) return MSV_ERR_NO_DEVICE;
         MSV_HIP(hipEventSynchronize(a.done));
         a.pending = false;
-        if (a.direct) {
-            if (scan_scores(a.direct, a.n) == MSV_OK) return MSV_OK;
-            // rare: classify from the bits the kernel latched in the slot's error word, and clear them
-            const int slot = static_cast<int>(&a - p->async);
-            uint32_t err = 0;
-            MSV_HIP(hipMemcpyAsync(&err, p->d_words + kErrWord + 1 + slot, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                   p->stream));
-            MSV_HIP(hipMemsetAsync(p->d_words + kErrWord + 1 + slot, 0, sizeof(uint32_t), p->stream));
-            MSV_HIP(hipStreamSynchronize(p->stream));
-            const msv_status e = err_status(err);
-            return e != MSV_OK ? e : scan_scores(a.direct, a.n);
-        }
+        // (direct: classified from the bits the kernel latched in the slot's error word, cleared there)
+        if (a.direct)
+            return host_scores_status(a.direct, a.n, &p, 1, p->stream, kErrWord + 1 + static_cast<int>(&a - p->async));
         return err_status(*a.h_err);
     }
     return MSV_ERR_INVALID_ARGUMENT;  // unknown ticket, or already waited for
@@ -1125,42 +1091,29 @@ msv_status msv_score_grid(msv_profile* const* profiles, uint32_t n_profiles, con
     // Page-locked residues are read in place and a page-locked destination is written by the kernels,
     // as in msv_score_batch.
     const uint64_t total = static_cast<uint64_t>(n_profiles) * n;
+    CsrStaging& sg = p0->host;
     const uint8_t* const zbase = (bytes && p0->zero_copy) ? mapped_host(residues) : nullptr;
     const uint8_t* const zres = zbase ? zbase + offsets[0] : nullptr;
     float* const direct = mapped_host(scores);
-    if (!zres) MSV_HIP(p0->d_res.reserve(std::max<uint64_t>(bytes, 1)));
-    MSV_HIP(p0->d_off.reserve(n + 1));
-    MSV_HIP(p0->d_order.reserve(n));
-    if (!direct) MSV_HIP(p0->d_scores.reserve(total));
-    MSV_HIP(p0->h_off.reserve(n + 8, hipHostMallocDefault));  // pinned: the offsets H2D is a true async DMA
+    MSV_HIP(sg.reserve_results(n, direct ? 0 : total));
     // an early error return leaves nothing queued that reads h_off or the staging buffers
-    msvrt::StreamDrain drain(st);
-    for (uint64_t k = 0; k <= n; ++k) p0->h_off[k] = offsets[k] - offsets[0];
-    const uint8_t* d_res = zres ? zres : p0->d_res;
-    if (bytes && !zres) MSV_HIP(hipMemcpyAsync(p0->d_res, residues + offsets[0], bytes, hipMemcpyHostToDevice, st));
-    MSV_HIP(hipMemcpyAsync(p0->d_off, p0->h_off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    StreamDrain drain(st);
+    MSV_HIP(sg.upload(residues, offsets, 0, n, !zres, st, st));
+    const uint8_t* d_res = zres ? zres : sg.d_res.get();
     // (a fused cooperative grid runs one workgroup per sequence: no dequeue order to sort; residues read
     // in place never take it)
     const bool sort = grid_choice(profiles, n_profiles, n, zres != nullptr).kind != msvplan::GridChoice::kCoopFused;
-    s = sort ? msv_order_longest_first(p0, p0->d_off, n, p0->d_order, st) : MSV_OK;
+    s = sort ? msv_order_longest_first(p0, sg.d_off, n, sg.d_order, st) : MSV_OK;
     if (s != MSV_OK) return s;
-    float* const dsc = direct ? direct : p0->d_scores;
-    s = score_grid_device(profiles, n_profiles, bytes ? d_res : p0->d_dummy, std::max<uint64_t>(bytes, 1), p0->d_off,
-                          n, sort ? p0->d_order.get() : nullptr, dsc, st, zres != nullptr);
+    float* const dsc = direct ? direct : sg.d_scores.get();
+    s = score_grid_device(profiles, n_profiles, sg.readable(d_res, bytes), std::max<uint64_t>(bytes, 1), sg.d_off, n,
+                          sort ? sg.d_order.get() : nullptr, dsc, st, zres != nullptr);
     if (s != MSV_OK) return s;
-    if (!direct) MSV_HIP(hipMemcpyAsync(scores, p0->d_scores, total * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (!direct) MSV_HIP(hipMemcpyAsync(scores, sg.d_scores, total * sizeof(float), hipMemcpyDeviceToHost, st));
     drain.disarm();
     MSV_HIP(hipStreamSynchronize(st));  // pageable host buffers above
-    // This call's errors show in its scores (+inf: bad residue, NaN: too long), so the profiles' latched
-    // error words are read back only when there is one (a 4-byte read-back per profile is a blit kernel
-    // plus a synchronisation: 24 profiles cost 0.9 ms, more than the whole grid's kernels).
-    if (scan_scores(scores, total) == MSV_OK) return MSV_OK;
-    msv_status first = MSV_OK;  // read back and clear EVERY profile's latched bits, report the first
-    for (uint32_t i = 0; i < n_profiles; ++i) {
-        s = msv_profile_check(profiles[i], st);
-        if (first == MSV_OK) first = s;
-    }
-    return first != MSV_OK ? first : scan_scores(scores, total);
+    // (the grid's launches latch their errors in the profiles' device-launch words)
+    return host_scores_status(scores, total, profiles, n_profiles, st, kErrWord);
 }
 
 // Host restatement of msvk::msv_pvalue_of (kept textually parallel; tests compare both).
@@ -1237,15 +1190,15 @@ msv_status msv_score_fasta_device(msv_profile* p, const msv_fasta_device* fasta,
     if (s != MSV_OK) return s;
     DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    MSV_HIP(p->d_scores.reserve(n));
-    MSV_HIP(p->d_order.reserve(n));
+    CsrStaging& sg = p->host;  // (only its order and scores: the inputs are the parser's)
+    MSV_HIP(sg.reserve_results(n, n));
     const uint64_t* d_off = msv_fasta_device_offsets(fasta);
-    s = msv_order_longest_first(p, d_off, n, p->d_order, p->stream);
+    s = msv_order_longest_first(p, d_off, n, sg.d_order, p->stream);
     if (s != MSV_OK) return s;
     s = msv_score_batch_device(p, msv_fasta_device_codes(fasta), std::max<uint64_t>(msv_fasta_device_residues(fasta), 1),
-                               d_off, n, p->d_order, p->d_scores, p->stream);
+                               d_off, n, sg.d_order, sg.d_scores, p->stream);
     if (s != MSV_OK) return s;
-    MSV_HIP(hipMemcpyAsync(scores, p->d_scores, n * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    MSV_HIP(hipMemcpyAsync(scores, sg.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, p->stream));
     return msv_profile_check(p, p->stream);
 }
 

@@ -23,10 +23,7 @@
 
 using msvrt::DeviceBuffer;
 using msvrt::DeviceGuard;
-using msvrt::kChunkBytes;  // per launch (msv_score_batch_device)
 
-// msv_device.cpp (library-internal): whether page-locked residues are read in place for this model and size.
-extern "C" bool msv_in_place_wins(const msv_profile* p, uint64_t bytes);
 // msv_device.cpp (library-internal): msv_score_batch_device for page-locked host residues (zero-copy twin).
 extern "C" msv_status msv_score_batch_host_residues(msv_profile* p, const uint8_t* d_residues, uint64_t residues_len,
                                          const uint64_t* d_offsets, uint64_t n, const uint32_t* d_order,
@@ -42,15 +39,12 @@ namespace {
 struct Rank {
     msv_profile* profile = nullptr;
     int device = -1;
+    uint32_t states = 0;  // of the profile's model
     // (declared before the buffers: a rank's members go in reverse order, the stream last, with the rank's
     // device current -- msv_multi_destroy)
     msvrt::Stream stream;
     ncclComm_t comm = nullptr;
-    DeviceBuffer<uint8_t> d_res;
-    DeviceBuffer<uint64_t> d_off;
-    DeviceBuffer<uint32_t> d_ord;
-    DeviceBuffer<float> d_sc;
-    std::vector<uint64_t> h_off;  // rebased offsets of the shard's current launch
+    msvrt::CsrStaging staged;  // the shard's current chunk; d_scores: the whole shard's scores
 };
 
 }  // namespace
@@ -77,42 +71,32 @@ const uint8_t* pinned_alias(const uint8_t* host) {
     return msvrt::mapped_host(host);
 }
 
-// Upload shard [first, last) to rank r's device and enqueue its order + kernel launches (one per
-// < 4 GiB chunk) on the rank's stream.  Runs on the rank's own host thread.
+// Upload shard [first, last) to rank r's device and enqueue its order + kernel launches on the rank's stream,
+// one per chunk of < 4 GiB of residues and fewer than kMaxLaunchSeqs sequences (msv_plan.h plan_pieces;
+// msv_profile_reserve_length has refused any sequence longer than a chunk).  Runs on the rank's own host
+// thread; msv_multi_score_batch drains the stream before it returns.
 msv_status enqueue_shard(Rank& r, const uint8_t* residues, const uint64_t* offsets, uint64_t first, uint64_t last) {
     DeviceGuard g(r.device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    const uint64_t cn = last - first;
-    MSV_HIP(r.d_sc.reserve(cn));
+    msvrt::CsrStaging& sg = r.staged;
+    const uint64_t cn = last - first, total = offsets[last] - offsets[first];
     // (copied instead where the kernel would outrun the in-place reads: small models, large shards)
-    const uint8_t* const zres =
-        msv_in_place_wins(r.profile, offsets[last] - offsets[first]) ? pinned_alias(residues) : nullptr;
-    uint64_t a = first;
-    while (a < last) {  // chunks addressing < kChunkBytes residues each
-        uint64_t b = a + 1;
-        while (b < last && offsets[b + 1] - offsets[a] < kChunkBytes) ++b;
-        if (offsets[b] - offsets[a] >= kChunkBytes) return MSV_ERR_SEQUENCE_TOO_LONG;
-        const uint64_t n = b - a, base = offsets[a], bytes = offsets[b] - base;
-        if (!zres) MSV_HIP(r.d_res.reserve(std::max<uint64_t>(bytes, 1)));
-        MSV_HIP(r.d_off.reserve(n + 1));
-        MSV_HIP(r.d_ord.reserve(n));
-        r.h_off.resize(n + 1);
-        for (uint64_t i = 0; i <= n; ++i) r.h_off[i] = offsets[a + i] - base;
-        MSV_HIP(hipMemcpyAsync(r.d_off, r.h_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, r.stream));
-        if (bytes && !zres) MSV_HIP(hipMemcpyAsync(r.d_res, residues + base, bytes, hipMemcpyHostToDevice, r.stream));
-        msv_status s = msv_order_longest_first(r.profile, r.d_off, n, r.d_ord, r.stream);
+    const uint8_t* const zres = msvplan::in_place_wins(r.states, total) ? pinned_alias(residues) : nullptr;
+    const std::vector<uint64_t> cut = msvplan::plan_pieces(offsets + first, cn, total, 0, 1);
+    for (size_t k = 0; k + 1 < cut.size(); ++k) {
+        const uint64_t a = first + cut[k], b = first + cut[k + 1], n = b - a, bytes = offsets[b] - offsets[a];
+        MSV_HIP(sg.reserve_results(n, cn));
+        MSV_HIP(sg.upload(residues, offsets, a, b, !zres, r.stream, r.stream));
+        msv_status s = msv_order_longest_first(r.profile, sg.d_off, n, sg.d_order, r.stream);
         if (s != MSV_OK) return s;
-        const uint8_t* src = (zres && bytes) ? zres + base : (bytes ? r.d_res.get() : nullptr);
-        if (!src) {  // an all-empty chunk still needs one readable byte
-            MSV_HIP(r.d_res.reserve(1));
-            src = r.d_res;
-        }
-        s = (zres && bytes ? msv_score_batch_host_residues : msv_score_batch_device)(
-            r.profile, src, std::max<uint64_t>(bytes, 1), r.d_off, n, r.d_ord, r.d_sc + (a - first), r.stream);
+        const bool in_place = zres && bytes;
+        const uint8_t* src = in_place ? zres + offsets[a] : sg.d_res.get();
+        s = (in_place ? msv_score_batch_host_residues : msv_score_batch_device)(
+            r.profile, sg.readable(src, bytes), std::max<uint64_t>(bytes, 1), sg.d_off, n, sg.d_order,
+            sg.d_scores + (a - first), r.stream);
         if (s != MSV_OK) return s;
-        // h_off (pageable) is rewritten by the next chunk: let this chunk's copy finish first
+        // the pinned offsets are rewritten by the next chunk: let this chunk's copy finish first
         if (b < last) MSV_HIP(hipStreamSynchronize(r.stream));
-        a = b;
     }
     return MSV_OK;
 }
@@ -148,10 +132,12 @@ msv_status msv_multi_create(msv_profile* const* profiles, uint32_t n_profiles, m
     if (!profiles || n_profiles == 0 || !out) return MSV_ERR_INVALID_ARGUMENT;
     *out = nullptr;
     std::vector<int> devs(n_profiles);
+    std::vector<uint32_t> states(n_profiles);
     for (uint32_t k = 0; k < n_profiles; ++k) {
         msv_kernel_info info;
         if (!profiles[k] || msv_profile_describe(profiles[k], &info) != MSV_OK) return MSV_ERR_INVALID_ARGUMENT;
         devs[k] = info.device;
+        states[k] = info.model_length - 1;
         for (uint32_t j = 0; j < k; ++j)
             if (devs[j] == devs[k]) return MSV_ERR_INVALID_ARGUMENT;  // one RCCL rank per device
     }
@@ -162,6 +148,7 @@ msv_status msv_multi_create(msv_profile* const* profiles, uint32_t n_profiles, m
         Rank& r = m->ranks[k];
         r.profile = profiles[k];
         r.device = devs[k];
+        r.states = states[k];
         DeviceGuard g(r.device);
         if (!g.ok || r.stream.create(hipStreamNonBlocking) != hipSuccess) {
             msv_multi_destroy(m);
@@ -200,6 +187,17 @@ msv_status msv_multi_score_batch(msv_multi* m, const uint8_t* residues, const ui
         if (!g.ok) return MSV_ERR_NO_DEVICE;
         MSV_HIP(m->d_all.reserve(n));
     }
+    // Every return from here on first waits for every rank's stream (idle already on success): a chunk's copy
+    // that reads a rank's pinned offsets, rewritten by the next call, may still be queued.
+    struct DrainRanks {
+        msv_multi* m;
+        ~DrainRanks() {
+            for (Rank& r : m->ranks) {
+                DeviceGuard g(r.device);
+                (void)hipStreamSynchronize(r.stream);
+            }
+        }
+    } drain{m};
     // 1. every rank uploads its shard and enqueues order + kernel, concurrently (one thread each)
     std::vector<msv_status> st(R, MSV_OK);
     std::vector<std::thread> workers;
@@ -222,7 +220,7 @@ msv_status msv_multi_score_batch(msv_multi* m, const uint8_t* residues, const ui
         if (!cnt) continue;
         Rank& r = m->ranks[k];
         if (hipSetDevice(r.device) != hipSuccess ||
-            ncclSend(r.d_sc, cnt, ncclFloat32, 0, r.comm, r.stream) != ncclSuccess ||
+            ncclSend(r.staged.d_scores, cnt, ncclFloat32, 0, r.comm, r.stream) != ncclSuccess ||
             hipSetDevice(m->ranks[0].device) != hipSuccess ||
             ncclRecv(m->d_all + b[k], cnt, ncclFloat32, static_cast<int>(k), m->ranks[0].comm,
                      m->ranks[0].stream) != ncclSuccess) {
@@ -237,11 +235,12 @@ msv_status msv_multi_score_batch(msv_multi* m, const uint8_t* residues, const ui
         MSV_HIP(hipMemcpyAsync(scores, m->d_all, n * sizeof(float), hipMemcpyDeviceToHost, m->ranks[0].stream));
         MSV_HIP(hipStreamSynchronize(m->ranks[0].stream));
     }
+    msv_status first = MSV_OK;  // every rank's bits are read and cleared (its stream waited for), the first reported
     for (Rank& r : m->ranks) {
         s = msv_profile_check(r.profile, r.stream);
-        if (s != MSV_OK) return s;
+        if (first == MSV_OK) first = s;
     }
-    return MSV_OK;
+    return first;
 }
 
 }  // extern "C"

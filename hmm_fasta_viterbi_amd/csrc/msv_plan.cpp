@@ -264,4 +264,23 @@ std::vector<uint64_t> plan_pieces(const uint64_t* offsets, uint64_t n, uint64_t 
     return cut;
 }
 
+void rebase_offsets(const uint64_t* offsets, uint64_t first, uint64_t last, uint64_t* out) {
+    const uint64_t base = offsets[first];
+    for (uint64_t i = first; i <= last; ++i) out[i - first] = offsets[i] - base;
+}
+
+bool in_place_wins(uint32_t states, uint64_t bytes) { return states >= kInPlaceMinStates || bytes < kInPlaceAnyBytes; }
+
+CallPlan plan_call(const uint64_t* offsets, uint64_t n, uint64_t total, bool in_place, uint32_t first_den,
+                   uint32_t growth) {
+    CallPlan c;
+    c.n = n;
+    c.mode = in_place && total ? CallPlan::kInPlace
+                               : (total <= kSmallCall && n <= kSmallCall ? CallPlan::kSmall : CallPlan::kCopied);
+    c.cut = plan_pieces(offsets, n, total, c.mode == CallPlan::kInPlace ? 0 : first_den, growth);
+    c.pipeline = c.mode == CallPlan::kCopied && c.pieces() > 1;
+    c.res_words = c.mode == CallPlan::kSmall ? (total + 7) / 8 : 0;
+    return c;
+}
+
 }  // namespace msvplan

@@ -88,13 +88,11 @@ struct msv_vit_profile {
     msvrt::LaunchRing<kLaunchSlots> kernels;  // the launch slots' streams and events
     msvrt::Stream stream;
     hipStream_t bound = nullptr;        // msv_vit_profile_bind_stream: a caller stream kept alive while bound
-    // msv_vit_score_batch / msv_vit_filter_batch staging
-    DeviceBuffer<uint8_t> d_res;
-    DeviceBuffer<uint64_t> d_off;
-    DeviceBuffer<float> d_sc;
+    // msv_vit_score_batch / msv_vit_filter_batch staging (staged.d_scores: the Viterbi scores); the filter's
+    // MSV scores and survivors list beside it
+    msvrt::CsrStaging staged;
     DeviceBuffer<float> d_msc_out;
     DeviceBuffer<uint32_t> d_sel;
-    DeviceBuffer<uint32_t> d_ord;
     hipEvent_t time_start = nullptr, time_stop = nullptr;  // msv_vit_debug_time_next_launch
     uint64_t* d_stamps = nullptr;                          // msv_vit_debug_set_stamps (tools only)
 };
@@ -371,7 +369,6 @@ msv_status msv_vit_score_batch(msv_vit_profile* p, const uint8_t* residues, cons
                                float* scores, void* stream) {
     if (!p || (n && (!offsets || !scores))) return MSV_ERR_INVALID_ARGUMENT;
     if (n == 0) return MSV_OK;
-    const uint64_t base = offsets[0];
     uint64_t longest = 0, total = 0;
     msv_status s = csr_extent(offsets, n, &longest, &total);
     if (s != MSV_OK) return s;
@@ -381,17 +378,16 @@ msv_status msv_vit_score_batch(msv_vit_profile* p, const uint8_t* residues, cons
     s = msv_vit_profile_reserve_length(p, longest);
     if (s != MSV_OK) return s;
     hipStream_t st = stream_of(p, stream);
-    std::vector<uint64_t> off(offsets, offsets + n + 1);
-    for (auto& o : off) o -= base;
-    MSV_HIP(p->d_res.reserve(total));
-    MSV_HIP(p->d_off.reserve(n + 1));
-    MSV_HIP(p->d_sc.reserve(n));
-    if (total) MSV_HIP(hipMemcpyAsync(p->d_res, residues + base, total, hipMemcpyHostToDevice, st));
-    MSV_HIP(hipMemcpyAsync(p->d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    s = launch(p, p->d_res, p->d_off, n, nullptr, nullptr, p->d_sc, st, p->d_words + kHostErrWord);
+    msvrt::CsrStaging& sg = p->staged;
+    MSV_HIP(sg.d_scores.reserve(n));
+    // an early error return leaves no copy queued that reads the pinned offsets (rewritten by the next call)
+    msvrt::StreamDrain drain(st);
+    MSV_HIP(sg.upload(residues, offsets, 0, n, true, st, st));
+    s = launch(p, sg.d_res, sg.d_off, n, nullptr, nullptr, sg.d_scores, st, p->d_words + kHostErrWord);
     if (s != MSV_OK) return s;
-    MSV_HIP(hipMemcpyAsync(scores, p->d_sc, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    return read_errors(p, kHostErrWord, st);
+    MSV_HIP(hipMemcpyAsync(scores, sg.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    drain.disarm();
+    return read_errors(p, kHostErrWord, st);  // synchronises
 }
 
 msv_status msv_filter_select_device(int device, const float* d_scores, const uint64_t* d_offsets,
@@ -421,7 +417,6 @@ msv_status msv_vit_filter_batch(msv_profile* msv, msv_vit_profile* vit, const ui
     msv_status s = msv_profile_describe(msv, &info);
     if (s != MSV_OK) return s;
     if (info.device != vit->device) return MSV_ERR_INVALID_ARGUMENT;
-    const uint64_t base = offsets[0];
     uint64_t longest = 0, total = 0;
     if ((s = csr_extent(offsets, n, &longest, &total)) != MSV_OK) return s;
     if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
@@ -431,35 +426,33 @@ msv_status msv_vit_filter_batch(msv_profile* msv, msv_vit_profile* vit, const ui
     if ((s = msv_profile_reserve_length(msv, longest)) != MSV_OK) return s;
     if ((s = msv_vit_profile_reserve_length(vit, longest)) != MSV_OK) return s;
     hipStream_t st = vit->stream;
-    std::vector<uint64_t> off(offsets, offsets + n + 1);
-    for (auto& o : off) o -= base;
-    MSV_HIP(vit->d_res.reserve(total));
-    MSV_HIP(vit->d_off.reserve(n + 1));
-    MSV_HIP(vit->d_sc.reserve(n));
+    msvrt::CsrStaging& sg = vit->staged;
+    MSV_HIP(sg.reserve_results(n, n));
     MSV_HIP(vit->d_msc_out.reserve(n));
     MSV_HIP(vit->d_sel.reserve(n));
-    MSV_HIP(vit->d_ord.reserve(n));
-    if (total) MSV_HIP(hipMemcpyAsync(vit->d_res, residues + base, total, hipMemcpyHostToDevice, st));
-    MSV_HIP(hipMemcpyAsync(vit->d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    // an early error return leaves no copy queued that reads the pinned offsets (rewritten by the next call)
+    msvrt::StreamDrain drain(st);
+    MSV_HIP(sg.upload(residues, offsets, 0, n, true, st, st));
     // MSV over every sequence, longest first
-    if ((s = msv_order_longest_first(msv, vit->d_off, n, vit->d_ord, st)) != MSV_OK) return s;
-    if ((s = msv_score_batch_device(msv, vit->d_res, total, vit->d_off, n, vit->d_ord, vit->d_msc_out, st)) != MSV_OK)
+    if ((s = msv_order_longest_first(msv, sg.d_off, n, sg.d_order, st)) != MSV_OK) return s;
+    if ((s = msv_score_batch_device(msv, sg.d_res, total, sg.d_off, n, sg.d_order, vit->d_msc_out, st)) != MSV_OK)
         return s;
     // survivors (P <= F1) -> Viterbi, all on the device; non-survivors keep -inf (0xff800000)
-    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(vit->d_sc.get()), static_cast<int>(0xff800000u), n, st));
+    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sg.d_scores.get()), static_cast<int>(0xff800000u), n, st));
     // survivors listed longest first (the MSV launch's order): the Viterbi launch's tail is its shortest ones
-    if ((s = msv_filter_select_device(vit->device, vit->d_msc_out, vit->d_off, vit->d_ord, n, msv_mu, msv_lambda, F1,
+    if ((s = msv_filter_select_device(vit->device, vit->d_msc_out, sg.d_off, sg.d_order, n, msv_mu, msv_lambda, F1,
                                       nullptr, vit->d_sel, vit->d_words + kSelWord, st)) != MSV_OK)
         return s;
-    if ((s = launch(vit, vit->d_res, vit->d_off, n, vit->d_sel, vit->d_words + kSelWord, vit->d_sc, st,
+    if ((s = launch(vit, sg.d_res, sg.d_off, n, vit->d_sel, vit->d_words + kSelWord, sg.d_scores, st,
                     vit->d_words + kHostErrWord)) != MSV_OK)
         return s;
     uint32_t count = 0;
     MSV_HIP(hipMemcpyAsync(msv_scores, vit->d_msc_out, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    MSV_HIP(hipMemcpyAsync(vit_scores, vit->d_sc, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    MSV_HIP(hipMemcpyAsync(vit_scores, sg.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipMemcpyAsync(&count, vit->d_words + kSelWord, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     std::vector<uint32_t> sel;
     MSV_HIP(hipStreamSynchronize(st));
+    drain.disarm();
     if (count) {
         sel.resize(count);
         MSV_HIP(hipMemcpyAsync(sel.data(), vit->d_sel, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -468,8 +461,10 @@ msv_status msv_vit_filter_batch(msv_profile* msv, msv_vit_profile* vit, const ui
     std::fill(passed, passed + n, static_cast<uint8_t>(0));
     for (uint32_t x : sel) passed[x] = 1;
     *n_passed = count;
-    if ((s = msv_profile_check(msv, st)) != MSV_OK) return s;
-    return read_errors(vit, kHostErrWord, st);
+    // both stages' words are read, so each call clears its own bits (a bad residue in a survivor latches both)
+    s = msv_profile_check(msv, st);
+    const msv_status vs = read_errors(vit, kHostErrWord, st);
+    return s != MSV_OK ? s : vs;
 }
 
 }  // extern "C"

@@ -8,7 +8,8 @@
 // (MSV_HMM.cpp:74-113) against the golden scores, msv_shard_bounds, the Viterbi stage's table builder
 // and CPU DP (msv_hmm_viterbi_scores, msv_vit_cpu_score), and the kernel-layout tables the device layer
 // uploads (table_layout.cpp: every MSV, cooperative and Viterbi layout, at exact-fit model lengths), and the MSV
-// plan policy (msv_plan.cpp) against the plans recorded on the device (tests/golden/msv_plans.json).
+// plan policy (msv_plan.cpp) against the plans recorded on the device (tests/golden/msv_plans.json), with the host
+// calls' part of it: rebase_offsets, plan_call's mode and staging layout, the multi-device chunk cuts.
 // Usage: sanitize_host <repo_root>
 #include <dirent.h>
 #include <unistd.h>
@@ -545,12 +546,135 @@ static void check_plan_pieces() {
     }
 }
 
+// 9d. rebase_offsets against a plain loop, bit for bit; the slots around the written range stay untouched
+static void check_rebase(const char* name, const std::vector<uint64_t>& o, uint64_t first, uint64_t last) {
+    const uint64_t kGuard = 0xfeedfacecafebeefull;
+    std::vector<uint64_t> got(last - first + 3, kGuard), want(last - first + 3, kGuard);  // exact heap size: ASan
+    msvplan::rebase_offsets(o.data(), first, last, got.data() + 1);
+    for (uint64_t i = first; i <= last; ++i) want[1 + i - first] = o[i] - o[first];
+    if (got != want) std::printf("  rebase_offsets: %s\n", name);
+    CHECK(got == want);
+}
+
+static void check_rebase_offsets() {
+    const uint64_t high = (1ull << 33) + 5;
+    check_rebase("first offset 0", csr(0, {{50, 7}, {3, 0}, {20, 1000}}), 0, 73);
+    check_rebase("first offset 2^33 + 5", csr(high, {{50, 7}, {3, 0}, {20, 1000}}), 0, 73);
+    check_rebase("a sub-range", csr(high, {{50, 7}, {3, 0}, {20, 1000}}), 11, 60);
+    check_rebase("empty sequences at both ends", csr(12, {{4, 0}, {30, 9}, {5, 0}}), 2, 37);
+    check_rebase("empty sequences at both ends, whole", csr(12, {{4, 0}, {30, 9}, {5, 0}}), 0, 39);
+    check_rebase("n = 1", csr(high, {{1, 300}}), 0, 1);
+    check_rebase("n = 1 inside", csr(3, {{9, 300}}), 4, 5);
+    check_rebase("n = 1, empty", csr(3, {{1, 0}}), 0, 1);
+}
+
+// 9e. plan_call: the mode the flags of msv_score_batch gave before the plan existed (zres / small / pipe,
+// printed by a scratch build of them for these inputs), and the layout of the call's staging words
+enum { kWantInPlace, kWantSmall, kWantCopiedOnePiece, kWantPipeline };
+
+static void check_call_plan(const char* name, const std::vector<uint64_t>& o, bool in_place, uint32_t first_den,
+                            uint32_t growth, int want) {
+    using msvplan::CallPlan;
+    const uint64_t n = o.size() - 1, total = o[n] - o[0];
+    const CallPlan c = msvplan::plan_call(o.data(), n, total, in_place, first_den, growth);
+    const size_t P = c.pieces();
+    const CallPlan::Mode mode = want == kWantInPlace ? CallPlan::kInPlace : want == kWantSmall ? CallPlan::kSmall : CallPlan::kCopied;
+    bool ok = c.mode == mode && c.pipeline == (want == kWantPipeline) && c.n == n;
+    ok = ok && c.cut == checked_pieces(o, in_place ? 0 : first_den, growth);
+    ok = ok && c.res_words == (want == kWantSmall ? (total + 7) / 8 : 0) && c.res_words * 8 >= (want == kWantSmall ? total : 0);
+    // regions of the staging words, in order: every piece's offsets, the small call's residues, the error word
+    std::vector<std::pair<uint64_t, uint64_t>> regions;  // [begin, end)
+    std::vector<uint64_t> staged(c.staged_words(), 0);    // exact heap size: a write past the layout is ASan's
+    for (size_t k = 0; k < P; ++k) {
+        ok = ok && c.offsets_word(k) == c.cut[k] + k;
+        regions.push_back({c.cut[k] + k, c.cut[k + 1] + k + 1});
+        msvplan::rebase_offsets(o.data(), c.cut[k], c.cut[k + 1], staged.data() + c.offsets_word(k));
+        ok = ok && staged[c.cut[k] + k] == 0 && staged[c.cut[k + 1] + k] == o[c.cut[k + 1]] - o[c.cut[k]];
+    }
+    regions.push_back({c.small_res_word(), c.small_res_word() + c.res_words});
+    regions.push_back({c.err_word(), c.err_word() + 1});
+    uint64_t at = 0;
+    for (const auto& r : regions) {  // back to back from word 0: none overlaps another, none leaves a gap
+        ok = ok && r.first == at && r.second >= r.first;
+        at = r.second;
+    }
+    ok = ok && at == c.staged_words() && c.staged_words() == n + P + c.res_words + 1 &&
+         c.upload_words() == n + P + c.res_words && c.err_word() >= c.upload_words();
+    if (!ok) std::printf("  plan_call: %s (n = %llu, total = %llu)\n", name, static_cast<unsigned long long>(n),
+                         static_cast<unsigned long long>(total));
+    CHECK(ok);
+}
+
+// ~12,000 sequences of ~500 residues, 2,000 empty records and one 150,000-residue record placed on the cuts of
+// the 4/2 plan (as tests/test_gpu_configs.py test_host_pipeline_piece_edges does)
+static std::vector<uint64_t> pipeline_offsets() {
+    std::mt19937_64 rng(41);
+    std::vector<uint64_t> lens(12000);
+    for (auto& L : lens) L = 300 + rng() % 401;
+    std::vector<uint64_t> o{0};
+    for (uint64_t L : lens) o.push_back(o.back() + L);
+    const std::vector<uint64_t> cut = msvplan::plan_pieces(o.data(), lens.size(), o.back(), 4, 2);
+    CHECK(cut.size() == 3);
+    const size_t edge = cut.size() > 2 ? cut[1] : lens.size() / 4;
+    lens.insert(lens.begin() + edge, 150000);  // the long record straddles the first cut
+    lens.insert(lens.begin() + edge, 700, 0);  // empty records before it, after it, and at both ends
+    lens.insert(lens.begin() + edge + 701, 700, 0);
+    lens.insert(lens.begin(), 300, 0);
+    lens.insert(lens.end(), 300, 0);
+    std::vector<uint64_t> out{77};
+    for (uint64_t L : lens) out.push_back(out.back() + L);
+    return out;
+}
+
+static void check_call_plans() {
+    using msvplan::kSmallCall;
+    for (uint64_t n : {1, 3})
+        for (uint64_t total : {uint64_t(0), uint64_t(1), uint64_t(7), uint64_t(8), uint64_t(9), kSmallCall, kSmallCall + 1}) {
+            std::vector<uint64_t> o{5};  // total residues over n sequences, the remainder in the last
+            for (uint64_t i = 0; i < n; ++i) o.push_back(o.back() + total / n + (i + 1 == n ? total % n : 0));
+            check_call_plan("small", o, false, 4, 2, total <= kSmallCall ? kWantSmall : kWantCopiedOnePiece);
+        }
+    const std::vector<uint64_t> o = pipeline_offsets();
+    CHECK(o.size() - 1 == 14001 && o.back() - o[0] >= msvplan::kPipelineMin);
+    check_call_plan("pipeline 4/2", o, false, 4, 2, kWantPipeline);
+    check_call_plan("pipeline 1/1", o, false, 1, 1, kWantCopiedOnePiece);
+    check_call_plan("in place 4/2", o, true, 4, 2, kWantInPlace);
+    check_call_plan("in place 1/1", o, true, 1, 1, kWantInPlace);
+    CHECK(msvplan::plan_call(o.data(), o.size() - 1, o.back() - o[0], false, 4, 2).pieces() == 2);
+    CHECK(msvplan::plan_call(o.data(), o.size() - 1, o.back() - o[0], true, 4, 2).pieces() == 1);
+    // the in-place rule's two thresholds
+    CHECK(msvplan::in_place_wins(300, 1ull << 30) && !msvplan::in_place_wins(299, 16ull << 20) &&
+          msvplan::in_place_wins(299, (16ull << 20) - 1));
+}
+
+// 9f. the multi-device chunks are plan_pieces' with first_den = 0: a shard under 4 GiB is one piece (what
+// msv_multi.cpp's own greedy loop gave), and 10 GiB in 1 MiB steps is cut into pieces under kChunkBytes that
+// are as long as the limit allows (the greedy loop's cuts)
+static void check_multi_chunks() {
+    CHECK((checked_pieces(csr(9, {{4000, 1u << 20}}), 0, 1) == std::vector<uint64_t>{0, 4000}));  // 3.9 GiB
+    CHECK((checked_pieces(pipeline_offsets(), 0, 1) == std::vector<uint64_t>{0, 14001}));
+    const std::vector<uint64_t> o = csr(0, {{10240, 1u << 20}});
+    const std::vector<uint64_t> cut = checked_pieces(o, 0, 1);
+    std::vector<uint64_t> greedy{0};
+    for (uint64_t a = 0; a < 10240;) {
+        uint64_t b = a + 1;
+        while (b < 10240 && o[b + 1] - o[a] < msvplan::kChunkBytes) ++b;
+        greedy.push_back(a = b);
+    }
+    CHECK(cut == greedy && cut.size() == 4);
+    for (size_t k = 0; k + 1 < cut.size(); ++k) CHECK(o[cut[k + 1]] - o[cut[k]] < msvplan::kChunkBytes);
+}
+
 static void check_plan_policy(const std::string& root) {
     const msvplan::Tables tables = plan_tables();
     CHECK(tables.variants.size() >= 80 && tables.coop.size() == 5);
     check_recorded_plans(root, tables);
     check_fused_grid(tables);
     check_plan_pieces();
+    check_rebase_offsets();
+    check_call_plans();
+    check_multi_chunks();
+    std::printf("  host staging: rebase_offsets on 8 ranges, plan_call on 18 calls, the multi-device chunks\n");
 }
 
 int main(int argc, char** argv) {

@@ -166,7 +166,7 @@ def test_host_pipeline_piece_edges():
 
 
 def test_pinned_small_model_large_batch_copied():
-    """Page-locked residues of a small model's large batch (< 300 states, >= 16 MiB: msv_device.cpp
+    """Page-locked residues of a small model's large batch (< 300 states, >= 16 MiB: msv_plan.h
     kInPlaceMinStates) are copied through the piece pipeline instead of read in place: bitwise equal to a
     device launch, with pageable and page-locked score destinations, and to the oracle on a sample."""
     e = msv.MSV_HMM(msv.Profile_HMM(profile_path("200.hmm")))
@@ -188,7 +188,7 @@ def test_pinned_small_model_large_batch_copied():
 
 
 def test_small_host_calls_staged():
-    """Pageable host calls of at most 1 MiB of residues (msv_device.cpp kSmallCall) send the residues in
+    """Pageable host calls of at most 1 MiB of residues (msv_plan.h kSmallCall) send the residues in
     the offsets' H2D and take the scores through pinned staging: bitwise equal to a device launch on
     both sides of the limit (1 MiB and 1 MiB + 1 residues), one-sequence calls of every length class,
     an all-empty batch, and a bad residue (raises; the next call is clean)."""
@@ -217,12 +217,13 @@ def test_small_host_calls_staged():
     e.close()
 
 
-def test_buffers_regrow_between_calls_of_different_sizes():
+def test_buffers_regrow_between_calls_of_different_sizes(tmp_path):
     """Batches of 1, 300 and 1 sequences (lengths 1..60) in that order on the SAME handles, so every staging
     buffer is allocated small, regrown, then reused larger than needed: score_batch with pageable arrays, with
     msv_host_alloc arrays, score_batch_async + wait, score_grid over two profiles (the MSV handle listed
-    twice) and the Viterbi host batch, each bitwise against the CPU oracle.  Then both handles are destroyed,
-    created again, and score the 1-sequence batch once more."""
+    twice), the Viterbi host batch, filter_pipeline (F1 = 1: every sequence survives), a one-device MultiGPU
+    context and score_fasta_device on the batch written out as FASTA, each bitwise against the CPU oracle.
+    Then the handles are destroyed, created again, and score the 1-sequence batch once more."""
     hmm = msv.Profile_HMM(profile_path("100.hmm"))
     o = OracleProfile("100")
     batches = [random_batch(610 + k, n, 1, 60) for k, n in enumerate((1, 300, 1))]
@@ -233,7 +234,9 @@ def test_buffers_regrow_between_calls_of_different_sizes():
         p[...] = a
         return p
 
-    def score_all(e, v, k):
+    letters = np.frombuffer(msv.AMINO_ACIDS.encode(), np.uint8)
+
+    def score_all(e, v, multi, k):
         (c, f), (w_msv, w_vit) = batches[k], want[k]
         n = len(f) - 1
         assert np.array_equal(bits(e.score_batch(codes=c, offsets=f)), bits(w_msv)), k
@@ -243,14 +246,64 @@ def test_buffers_regrow_between_calls_of_different_sizes():
         grid = msv.score_grid([e, e], codes=c, offsets=f)
         assert np.array_equal(bits(grid), bits(np.stack([w_msv, w_msv]))), k
         assert np.array_equal(bits(v.score_batch(codes=c, offsets=f)), bits(w_vit)), k
+        msc, passed, vsc, _ = msv.filter_pipeline(e, v, codes=c, offsets=f, F1=1.0)
+        assert np.array_equal(bits(msc), bits(w_msv)), k
+        assert np.array_equal(bits(vsc), bits(w_vit)), k
+        assert passed.all() and len(passed) == n, k
+        assert np.array_equal(bits(multi.score_batch(codes=c, offsets=f)), bits(w_msv)), k
+        path = tmp_path / f"batch{k}.fsa"
+        path.write_bytes(b"".join(b">s%d\n" % i + letters[c[int(f[i]):int(f[i + 1])]].tobytes() + b"\n"
+                                  for i in range(n)))
+        dev = msv.FASTA_device(str(path))
+        assert dev.count == n and dev.rejected == 0
+        assert np.array_equal(bits(e.score_fasta_device(dev)), bits(w_msv)), k
+        dev.close()
 
-    e, v = msv.MSV_HMM(hmm), msv.Viterbi_HMM(hmm)
+    def handles():
+        e = msv.MSV_HMM(hmm)
+        return e, msv.Viterbi_HMM(hmm), msv.MultiGPU([e])
+
+    e, v, multi = handles()
     for k in range(3):
-        score_all(e, v, k)
+        score_all(e, v, multi, k)
+    multi.close()
     e.close()
     v.close()
+    e, v, multi = handles()
+    score_all(e, v, multi, 0)
+    multi.close()
+    e.close()
+    v.close()
+
+
+def test_error_then_clean_on_the_pinned_offsets_paths():
+    """The Viterbi host batch, filter_pipeline and a MultiGPU context stage their rebased offsets in pinned
+    memory: a bad residue (code 20 in the last of 3 sequences of lengths 5, 0 and 60; a latched error bit, not
+    a fault) raises IndexError on each, and the next call on the clean batch equals the CPU oracle bitwise."""
+    hmm = msv.Profile_HMM(profile_path("100.hmm"))
+    o = OracleProfile("100")
+    rng = np.random.default_rng(631)
+    codes = rng.integers(0, 20, 65).astype(np.uint8)
+    offsets = np.array([0, 5, 5, 65], np.uint64)
+    bad = codes.copy()
+    bad[40] = 20
+    w_msv, w_vit = o.score_batch(codes, offsets), o.vit_score_batch(codes, offsets)
     e, v = msv.MSV_HMM(hmm), msv.Viterbi_HMM(hmm)
-    score_all(e, v, 0)
+    multi = msv.MultiGPU([e])
+
+    with pytest.raises(IndexError):
+        v.score_batch(codes=bad, offsets=offsets)
+    assert np.array_equal(bits(v.score_batch(codes=codes, offsets=offsets)), bits(w_vit))
+
+    with pytest.raises(IndexError):
+        msv.filter_pipeline(e, v, codes=bad, offsets=offsets, F1=1.0)
+    msc, passed, vsc, _ = msv.filter_pipeline(e, v, codes=codes, offsets=offsets, F1=1.0)
+    assert np.array_equal(bits(msc), bits(w_msv)) and np.array_equal(bits(vsc), bits(w_vit)) and passed.all()
+
+    with pytest.raises(IndexError):
+        multi.score_batch(codes=bad, offsets=offsets)
+    assert np.array_equal(bits(multi.score_batch(codes=codes, offsets=offsets)), bits(w_msv))
+    multi.close()
     e.close()
     v.close()
 
