@@ -29,7 +29,7 @@ __all__ = [
     "AMINO_ACIDS", "MSVError", "Profile_HMM", "FASTA_protein_sequences", "MSV_HMM", "pack_sequences",
     "encode", "sequence_transitions", "device_count", "score_grid", "score_grid_device", "score_batch_multi",
     "shard_bounds", "FASTA_device", "MultiGPU", "Viterbi_HMM", "filter_pipeline", "INSERTS_ZERO",
-    "INSERTS_LOG_ODDS",
+    "INSERTS_LOG_ODDS", "Traces",
 ]
 
 INSERTS_ZERO = 0      # HMMER3's insert scores (background emissions: 0)
@@ -342,6 +342,88 @@ class MSV_HMM:
         self.close()
 
 
+class Traces:
+    """One optimal Viterbi state path per traced sequence (msv.h "Viterbi traces"): `scores` float32 [n],
+    `domain_offsets` uint64 [n + 1] (entry q's domains are domains[domain_offsets[q]:domain_offsets[q + 1]]),
+    `domains` a structured array (seq, i_from, i_to, k_from, k_to, ops_len, ops_begin) and `ops`, one byte
+    'M' / 'I' / 'D' per core state visited.  `status` is the call's status name (MSV_OK, or the scoring calls'
+    error when strict=False let a bad sequence through with no domains); `stats` what the device did."""
+
+    def __init__(self, scores, domain_offsets, domains, ops, *, status="MSV_OK", stats=None, codes=None,
+                 offsets=None, consensus=None):
+        self.scores, self.domain_offsets, self.domains, self.ops = scores, domain_offsets, domains, ops
+        self.status = status
+        self.stats = stats or {}
+        self._codes, self._offsets, self._consensus = codes, offsets, consensus
+
+    def __len__(self):
+        return len(self.scores)
+
+    def domains_of(self, q: int) -> np.ndarray:
+        return self.domains[int(self.domain_offsets[q]):int(self.domain_offsets[q + 1])]
+
+    def ops_of(self, d) -> bytes:
+        return self.ops[int(d["ops_begin"]):int(d["ops_begin"]) + int(d["ops_len"])].tobytes()
+
+    def path(self, q: int):
+        """The core states of entry q's path in order, as (state, k, i) with state in 'MID' (a D keeps the i of
+        the residue before it); the specials follow from the domains."""
+        for d in self.domains_of(q):
+            i, k = int(d["i_from"]) - 1, int(d["k_from"]) - 1
+            for op in self.ops_of(d):
+                if op == 77:    # M
+                    i, k = i + 1, k + 1
+                elif op == 73:  # I
+                    i += 1
+                else:           # D
+                    k += 1
+                yield chr(op), k, i
+
+    def alignment(self, q: int, d: int) -> str:
+        """Domain d of entry q as three lines: the model's consensus residues ('.' opposite an insert), a match
+        line ('|' identical, '+' a positive match score, ' ' otherwise) and the sequence ('-' opposite a delete)."""
+        if self._codes is None or self._consensus is None:
+            raise ValueError("these traces carry no sequences or model to align")
+        dom = self.domains_of(q)[d]
+        o0 = int(self._offsets[int(dom["seq"])])
+        cons, positive = self._consensus
+        top, mid, bot = [], [], []
+        i, k = int(dom["i_from"]) - 1, int(dom["k_from"]) - 1
+        for op in self.ops_of(dom):
+            if op == 77:
+                i, k = i + 1, k + 1
+                r = int(self._codes[o0 + i - 1])
+                top.append(AMINO_ACIDS[cons[k]])
+                mid.append("|" if r == cons[k] else "+" if positive[r, k] else " ")
+                bot.append(AMINO_ACIDS[r])
+            elif op == 73:
+                i += 1
+                top.append(".")
+                mid.append(" ")
+                bot.append(AMINO_ACIDS[int(self._codes[o0 + i - 1])].lower())
+            else:
+                k += 1
+                top.append(AMINO_ACIDS[cons[k]])
+                mid.append(" ")
+                bot.append("-")
+        return "\n".join("".join(x) for x in (top, mid, bot))
+
+
+def _cpu_trace(msc, isc, tsc, consts, codes):
+    """msv_vit_cpu_trace by its two-call sizing protocol -> (status, score, domains, ops)."""
+    L = _native.lib()
+    codes = np.ascontiguousarray(codes, np.uint8)
+    sc, nd, no = C.c_float(), C.c_uint32(), C.c_uint64()
+    args = (msc.ctypes.data, None if isc is None else isc.ctypes.data, tsc.ctypes.data, msc.shape[1],
+            *[float(x) for x in consts], codes.ctypes.data if codes.size else None, codes.size)
+    st = L.msv_vit_cpu_trace(*args, C.byref(sc), C.byref(nd), C.byref(no), None, None)
+    doms = np.zeros(nd.value if st == 0 else 0, _native.DOMAIN_DTYPE)
+    ops = np.zeros(no.value if st == 0 else 0, np.uint8)
+    if st == 0 and nd.value:
+        st = L.msv_vit_cpu_trace(*args, C.byref(sc), C.byref(nd), C.byref(no), doms.ctypes.data, ops.ctypes.data)
+    return st, np.float32(sc.value), doms, ops
+
+
 class Viterbi_HMM:
     """Viterbi stage for one profile on one GPU: HMMER3's generic local Viterbi over the
     reference's parse (insert emissions, 7 transitions per node: Profile_HMM.cpp:107-120) with the MSV
@@ -402,6 +484,76 @@ class Viterbi_HMM:
         check(st, "msv_vit_score_batch")
         return out
 
+    def _consensus(self):
+        return self.match_scores.argmax(axis=0), self.match_scores > 0
+
+    def trace_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
+                    offsets: np.ndarray | None = None, select=None, workspace_bytes: int = 0,
+                    strict: bool = True) -> Traces:
+        """Score and one optimal path of the selected sequences (all when select is None), computed on the GPU
+        (msv_vit_trace_batch), per select entry in the caller's order.  workspace_bytes bounds the device memory
+        for back-pointers (0: the default of trace_describe()); the call runs in as many chunks as that takes.
+        A bad residue raises IndexError as score_batch does, unless strict=False: then the traces are returned
+        with `status` set, the bad entries without domains."""
+        if seqs is not None:
+            codes, offsets = pack_sequences(seqs)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        sel = None if select is None else np.ascontiguousarray(select, np.uint32)
+        sel_buf = sel if sel is None or sel.size else np.zeros(1, np.uint32)  # (an empty list is not "every one")
+        L = _native.lib()
+        t = C.c_void_p()
+        st = L.msv_vit_trace_batch(self._p, codes.ctypes.data if codes.size else None, offsets.ctypes.data, n,
+                                   None if sel is None else sel_buf.ctypes.data,
+                                   0 if sel is None else sel.size, workspace_bytes, C.byref(t))
+        if not t.value:
+            check(st, "msv_vit_trace_batch")
+        try:
+            if st != _native.MSV_OK and strict:
+                if st == _native.MSV_ERR_BAD_RESIDUE:
+                    raise IndexError("residue outside the 20 amino acids")
+                check(st, "msv_vit_trace_batch")
+            m = L.msv_vit_traces_count(t)
+            scores = np.zeros(m, np.float32)
+            dom_off = np.zeros(m + 1, np.uint64)
+            doms = np.zeros(L.msv_vit_traces_domains(t), _native.DOMAIN_DTYPE)
+            ops = np.zeros(L.msv_vit_traces_ops(t), np.uint8)
+            check(L.msv_vit_traces_copy(t, scores.ctypes.data, dom_off.ctypes.data, doms.ctypes.data,
+                                        ops.ctypes.data), "msv_vit_traces_copy")
+            stats = _native.VitTraceStats()
+            check(L.msv_vit_traces_stats(t, C.byref(stats)))
+        finally:
+            L.msv_vit_traces_free(t)
+        return Traces(scores, dom_off, doms, ops, status=_native.STATUS.get(st, str(st)),
+                      stats={f: getattr(stats, f) for f, _ in stats._fields_}, codes=codes, offsets=offsets,
+                      consensus=self._consensus())
+
+    def trace_on_sequence(self, seq=None, *, codes: np.ndarray | None = None) -> Traces:
+        """The serial CPU trace of one sequence (msv_vit_cpu_trace): the same path as trace_batch, bit for bit."""
+        if seq is not None:
+            codes = encode(seq[1:] if seq.startswith("#") else seq)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        st, sc, doms, ops = _cpu_trace(self.match_scores, self.insert_scores if self.insert_mode else None,
+                                       self.transition_scores, (self.tr_B_Mk, self.tr_E_C, self.tr_E_J), codes)
+        if st == _native.MSV_ERR_BAD_RESIDUE:
+            raise IndexError("residue outside the 20 amino acids")
+        check(st, "msv_vit_cpu_trace")
+        return Traces(np.array([sc], np.float32), np.array([0, len(doms)], np.uint64), doms, ops, codes=codes,
+                      offsets=np.array([0, codes.size], np.uint64), consensus=self._consensus())
+
+    @staticmethod
+    def trace_plans() -> list[tuple[str, int]]:
+        """The compiled trace plans as (name, capacity in states), by rising capacity."""
+        L = _native.lib()
+        return [(L.msv_vit_trace_plan_name(i).decode(), int(L.msv_vit_trace_plan_capacity(i)))
+                for i in range(L.msv_vit_trace_plan_count())]
+
+    def trace_describe(self) -> dict:
+        info = _native.VitTraceInfo()
+        check(_native.lib().msv_vit_trace_describe(self._p, C.byref(info)), "msv_vit_trace_describe")
+        return info.as_dict()
+
     def score_batch_device(self, residues_ptr: int, residues_len: int, offsets_ptr: int, n: int, scores_ptr: int,
                            select_ptr: int | None = None, select_count_ptr: int | None = None,
                            stream: int | None = None) -> None:
@@ -460,10 +612,13 @@ class Viterbi_HMM:
 
 
 def filter_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, seqs: Sequence[str] | None = None, *,
-                    codes: np.ndarray | None = None, offsets: np.ndarray | None = None, F1: float = 0.02):
+                    codes: np.ndarray | None = None, offsets: np.ndarray | None = None, F1: float = 0.02,
+                    align: bool = False):
     """HMMER3's MSV -> Viterbi cascade on the GPU (msv_vit_filter_batch): MSV scores of every sequence,
     the survivors P <= F1 (STATS LOCAL MSV), their Viterbi scores (-inf elsewhere) and Viterbi P-values
-    (STATS LOCAL VITERBI, NaN elsewhere).  Returns (msv_scores, passed, vit_scores, vit_pvalues)."""
+    (STATS LOCAL VITERBI, NaN elsewhere).  Returns (msv_scores, passed, vit_scores, vit_pvalues); with
+    align=True also the Traces of the sequences that passed, in index order (a second call that uploads the
+    batch again: Viterbi_HMM.trace_batch with select = the passed indices)."""
     if seqs is not None:
         codes, offsets = pack_sequences(seqs)
     codes = np.ascontiguousarray(codes, np.uint8)
@@ -483,6 +638,9 @@ def filter_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, seqs: Sequence
     vpv = np.full(n, np.nan)
     if mask.any():
         vpv[mask] = vit_engine.pvalues(vsc, offsets)[mask]
+    if align:
+        traces = vit_engine.trace_batch(codes=codes, offsets=offsets, select=np.flatnonzero(mask).astype(np.uint32))
+        return msc, mask, vsc, vpv, traces
     return msc, mask, vsc, vpv
 
 

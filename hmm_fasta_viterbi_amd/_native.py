@@ -54,6 +54,10 @@ EXPORTED = [
     "msv_vit_profile_describe", "msv_vit_variant_count", "msv_vit_variant_name", "msv_vit_profile_set_variant",
     "msv_vit_score_batch_device", "msv_vit_score_batch", "msv_vit_profile_check", "msv_vit_filter_batch",
     "msv_vit_profile_bind_stream",
+    "msv_vit_cpu_trace", "msv_vit_trace_plan_count", "msv_vit_trace_plan_name", "msv_vit_trace_plan_capacity",
+    "msv_vit_trace_plan_cell", "msv_vit_trace_sequence_bytes", "msv_vit_trace_chunk_cuts", "msv_vit_trace_batch",
+    "msv_vit_traces_count", "msv_vit_traces_domains", "msv_vit_traces_ops", "msv_vit_traces_copy",
+    "msv_vit_traces_free", "msv_vit_trace_describe", "msv_vit_traces_stats",
 ]
 
 
@@ -117,6 +121,48 @@ class VitInfo(C.Structure):
         d = {f: getattr(self, f) for f, _ in self._fields_}
         d["variant"] = self.variant.decode()
         return d
+
+
+class VitDomain(C.Structure):
+    """msv_vit_domain; DOMAIN_DTYPE is the same record as a numpy structured dtype."""
+    _fields_ = [
+        ("seq", C.c_uint32),
+        ("i_from", C.c_uint32),
+        ("i_to", C.c_uint32),
+        ("k_from", C.c_uint32),
+        ("k_to", C.c_uint32),
+        ("ops_len", C.c_uint32),
+        ("ops_begin", C.c_uint64),
+    ]
+
+
+DOMAIN_DTYPE = [("seq", "<u4"), ("i_from", "<u4"), ("i_to", "<u4"), ("k_from", "<u4"), ("k_to", "<u4"),
+                ("ops_len", "<u4"), ("ops_begin", "<u8")]
+
+
+class VitTraceInfo(C.Structure):
+    _fields_ = [
+        ("plan", C.c_char * 64),
+        ("states_per_lane", C.c_uint32),
+        ("lanes_per_sequence", C.c_uint32),
+        ("capacity", C.c_uint32),
+        ("scratch_bytes", C.c_uint32),
+        ("words_per_lane", C.c_uint32),
+        ("blocks", C.c_uint32),
+        ("lds_bytes", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("default_workspace_bytes", C.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
+        d["plan"] = self.plan.decode()
+        return d
+
+
+class VitTraceStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint64), ("pointer_bytes", C.c_uint64), ("fill_ms", C.c_float),
+                ("walk_ms", C.c_float)]
 
 
 _lib = None
@@ -220,6 +266,22 @@ def lib() -> C.CDLL:
         "msv_vit_profile_check": (C.c_int, [vp, vp]),
         "msv_vit_filter_batch": (C.c_int, [vp, vp, vp, vp, u64, f32, f32, C.c_double, vp, vp, vp,
                                            C.POINTER(C.c_uint64)]),
+        "msv_vit_cpu_trace": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, u64, fp, C.POINTER(u32),
+                                        C.POINTER(u64), vp, vp]),
+        "msv_vit_trace_plan_count": (C.c_int, []),
+        "msv_vit_trace_plan_name": (C.c_char_p, [C.c_int]),
+        "msv_vit_trace_plan_capacity": (u32, [C.c_int]),
+        "msv_vit_trace_plan_cell": (C.c_int, [C.c_int, u32] + [C.POINTER(u32)] * 5),
+        "msv_vit_trace_sequence_bytes": (u64, [C.c_int, u64]),
+        "msv_vit_trace_chunk_cuts": (C.c_int, [vp, u64, u64, vp, C.POINTER(u64)]),
+        "msv_vit_trace_batch": (C.c_int, [vp, vp, vp, u64, vp, u64, u64, C.POINTER(vp)]),
+        "msv_vit_traces_count": (u64, [vp]),
+        "msv_vit_traces_domains": (u64, [vp]),
+        "msv_vit_traces_ops": (u64, [vp]),
+        "msv_vit_traces_copy": (C.c_int, [vp, vp, vp, vp, vp]),
+        "msv_vit_traces_free": (None, [vp]),
+        "msv_vit_trace_describe": (C.c_int, [vp, C.POINTER(VitTraceInfo)]),
+        "msv_vit_traces_stats": (C.c_int, [vp, C.POINTER(VitTraceStats)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

@@ -11,6 +11,7 @@
 
 #include "host_cpu.h"
 #include "msv.h"
+#include "vit_trace_plan.h"
 
 extern "C" {
 
@@ -98,6 +99,33 @@ msv_status msv_vit_cpu_score(const float* match_scores, const float* insert_scor
         if (codes[i] >= 20) return MSV_ERR_BAD_RESIDUE;
     *score = msv_host::viterbi_run_on_sequence(match_scores, insert_scores, transition_scores, model_length, tr_B_Mk,
                                                tr_E_C, tr_E_J, codes, L);
+    return MSV_OK;
+}
+
+msv_status msv_vit_cpu_trace(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                             uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                             uint64_t L, float* score, uint32_t* n_domains, uint64_t* n_ops, msv_vit_domain* domains,
+                             uint8_t* ops) {
+    if (!match_scores || !transition_scores || !score || !n_domains || !n_ops || model_length < 2 || (L && !codes) ||
+        (domains == nullptr) != (ops == nullptr))
+        return MSV_ERR_INVALID_ARGUMENT;
+    // msv_vit_profile_create's rule: with every transition <= 0 no D beats its row's best M, so E exits from M
+    for (size_t k = 1; k + 1 < model_length; ++k)
+        for (int t = 0; t < 7; ++t)
+            if (!(transition_scores[k * 7 + t] <= 0.0f)) return MSV_ERR_INVALID_ARGUMENT;
+    for (uint64_t i = 0; i < L; ++i)
+        if (codes[i] >= 20) return MSV_ERR_BAD_RESIDUE;
+    const msv_host::VitTrace t = msv_host::viterbi_trace_on_sequence(
+        match_scores, insert_scores, transition_scores, model_length, tr_B_Mk, tr_E_C, tr_E_J, codes, L);
+    *score = t.score;
+    if (domains) {
+        // the second call of the sizing protocol: the caller's buffers hold the counts of the first
+        if (*n_domains < t.domains.size() || *n_ops < t.ops.size()) return MSV_ERR_INVALID_ARGUMENT;
+        std::copy(t.domains.begin(), t.domains.end(), domains);
+        std::copy(t.ops.begin(), t.ops.end(), ops);
+    }
+    *n_domains = static_cast<uint32_t>(t.domains.size());
+    *n_ops = t.ops.size();
     return MSV_OK;
 }
 
@@ -203,6 +231,122 @@ float viterbi_run_on_sequence(const float* msc, const float* isc, const float* t
         B = std::max(N + move, J + move);
     }
     return C + move;
+}
+
+VitTrace viterbi_trace_on_sequence(const float* msc, const float* isc, const float* tsc, size_t M, float tr_B_Mk,
+                                   float tr_E_C, float tr_E_J, const uint8_t* codes, size_t L) {
+    // viterbi_run_on_sequence's DP, keeping 4 source bits per cell and one record per row (vit_trace_plan.h),
+    // then the walk back from C(L).  A source is found by EQUALITY on final values, candidates in msv.h's
+    // tie-break order: every term is one float add and max is exact, so the GPU (vit_trace.hip) finds the same.
+    using namespace vittrace;
+    constexpr float ninf = -std::numeric_limits<float>::infinity();
+    enum { MM, MI, MD, IM, II, DM, DD };
+    const size_t K = M - 1;
+    float loop, move;
+    msv_sequence_transitions(L, &loop, &move);
+    std::vector<float> Mv(M, ninf), Iv(M, ninf), Dv(M, ninf);
+    std::vector<uint8_t> cell(L * K);  // [row i-1][node k-1]
+    std::vector<uint32_t> rec(L);
+    float J = ninf, C = ninf, N = 0.0f, B = move;
+    for (size_t i = 0; i < L; ++i) {
+        const size_t r = codes[i];
+        const float* ms = msc + r * M;
+        const float* is = isc ? isc + r * M : nullptr;
+        uint8_t* bits = cell.data() + i * K;  // bits[k - 1]
+        const float Bt = B + tr_B_Mk;
+        float E = ninf;
+        for (size_t k = K; k >= 1; --k) {
+            const float* tp = tsc + (k - 1) * 7;  // into node k from node k-1
+            uint32_t b = 0;
+            if (k < K) {
+                const float* tk = tsc + k * 7;
+                const float mi = Mv[k] + tk[MI], ii = Iv[k] + tk[II];
+                const float iv = std::max(mi, ii);
+                if (!(iv == mi)) b |= kIFromI;
+                Iv[k] = is ? iv + is[k] : iv;
+            } else {
+                Iv[k] = ninf;  // no insert state at node K
+            }
+            const float cm = k > 1 ? Mv[k - 1] + tp[MM] : ninf, ci = k > 1 ? Iv[k - 1] + tp[IM] : ninf,
+                        cd = k > 1 ? Dv[k - 1] + tp[DM] : ninf;
+            const float mx = std::max(std::max(cm, ci), std::max(cd, Bt));
+            b |= mx == cm ? kFromM : mx == ci ? kFromI : mx == cd ? kFromD : kFromB;
+            Mv[k] = mx + ms[k];
+            E = std::max(E, Mv[k]);
+            bits[k - 1] = static_cast<uint8_t>(b);
+        }
+        Dv[1] = ninf;  // entered from node 0, which only B leaves
+        for (size_t k = 2; k <= K; ++k) {
+            const float* tp = tsc + (k - 1) * 7;
+            const float md = Mv[k - 1] + tp[MD], dd = Dv[k - 1] + tp[DD];
+            Dv[k] = std::max(md, dd);
+            if (!(Dv[k] == md)) bits[k - 1] |= kDFromD;
+        }
+        size_t kE = 1;
+        while (kE < K && !(Mv[kE] == E)) ++kE;  // the smallest k with M(i,k) == E(i)
+        E = std::max(E, Dv[K]);                 // (the score's own E; no D exceeds it, msv_vit_cpu_trace checks)
+        const float Jl = J + loop, Cl = C + loop;
+        J = std::max(Jl, E + tr_E_J);
+        C = std::max(Cl, E + tr_E_C);
+        N = N + loop;
+        const float Bn = N + move;
+        B = std::max(Bn, J + move);
+        rec[i] = static_cast<uint32_t>(kE) | (C == Cl ? 0u : kRecCFromE) | (J == Jl ? 0u : kRecJFromE) |
+                 (B == Bn ? 0u : kRecBFromJ);
+    }
+    VitTrace t;
+    t.score = C + move;
+    if (L == 0 || !std::isfinite(t.score)) return t;
+    // the walk, last domain first; ops and domains are reversed at the end
+    size_t i = L;
+    while (i >= 1 && !(rec[i - 1] & kRecCFromE)) --i;  // C loops
+    while (i >= 1) {
+        // E(i) -> M(i, k)
+        size_t k = rec[i - 1] & kRecKMask;
+        msv_vit_domain d{};
+        d.i_to = static_cast<uint32_t>(i);
+        d.k_to = static_cast<uint32_t>(k);
+        const size_t ops0 = t.ops.size();
+        enum { sM, sI, sD } st = sM;
+        bool entered = false;
+        while (!entered && i >= 1 && k >= 1) {
+            const uint32_t b = cell[(i - 1) * K + (k - 1)];
+            if (st == sM) {
+                t.ops.push_back('M');
+                const uint32_t src = b & 3u;
+                if (src == kFromB) {
+                    entered = true;
+                    d.i_from = static_cast<uint32_t>(i);
+                    d.k_from = static_cast<uint32_t>(k);
+                } else {
+                    st = src == kFromM ? sM : src == kFromI ? sI : sD;
+                }
+                --i;
+                --k;
+            } else if (st == sI) {
+                t.ops.push_back('I');
+                st = (b & kIFromI) ? sI : sM;
+                --i;
+            } else {
+                t.ops.push_back('D');
+                st = (b & kDFromD) ? sD : sM;
+                --k;
+            }
+        }
+        d.ops_len = static_cast<uint32_t>(t.ops.size() - ops0);
+        t.domains.push_back(d);
+        // B(i): from N (the path's start) or from J, which loops back to an earlier E
+        if (!entered || i == 0 || !(rec[i - 1] & kRecBFromJ)) break;
+        while (i >= 1 && !(rec[i - 1] & kRecJFromE)) --i;
+    }
+    std::reverse(t.ops.begin(), t.ops.end());
+    std::reverse(t.domains.begin(), t.domains.end());
+    uint64_t at = 0;
+    for (msv_vit_domain& d : t.domains) {
+        d.ops_begin = at;
+        at += d.ops_len;
+    }
+    return t;
 }
 
 }  // namespace msv_host

@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "msv.h"
+
 namespace msv_host {
 
 // MSV_HMM::run_on_sequence (MSV_HMM.cpp:74-113) on codes 0..19: emission_scores is the [20][M]
@@ -16,6 +18,16 @@ float run_on_sequence(const float* emission_scores, size_t M, float tr_B_Mk, flo
 // zero insert scores), tsc [M][7] log transitions.
 float viterbi_run_on_sequence(const float* msc, const float* isc, const float* tsc, size_t M, float tr_B_Mk,
                               float tr_E_C, float tr_E_J, const uint8_t* codes, size_t L);
+
+// The same DP with back-pointers, walked back from C(L): the score (viterbi_run_on_sequence's bits) and one
+// optimal path as domains and ops (msv.h, msv_vit_cpu_trace; seq = 0, ops_begin from 0).
+struct VitTrace {
+    float score = 0;
+    std::vector<msv_vit_domain> domains;
+    std::vector<uint8_t> ops;
+};
+VitTrace viterbi_trace_on_sequence(const float* msc, const float* isc, const float* tsc, size_t M, float tr_B_Mk,
+                                   float tr_E_C, float tr_E_J, const uint8_t* codes, size_t L);
 
 // Kernel-layout tables (table_layout.cpp, where the layouts are written out), from the [20][model_length]
 // residue-major host tables.  The device layer uploads them as they are.

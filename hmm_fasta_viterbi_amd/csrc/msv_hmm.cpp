@@ -253,6 +253,43 @@ std::vector<Log_score> Viterbi_HMM::score_batch(const Packed_sequences& packed) 
     return out;
 }
 
+Viterbi_traces Viterbi_HMM::trace_batch(const Packed_sequences& packed, const std::vector<uint32_t>& select, bool all,
+                                        uint64_t workspace_bytes) {
+    msv_vit_traces* t = nullptr;
+    const bool every = all && select.empty();
+    const msv_status s = msv_vit_trace_batch(profile_, packed.codes.data(), packed.offsets.data(), packed.size(),
+                                             every ? nullptr : select.data(), select.size(), workspace_bytes, &t);
+    if (s == MSV_ERR_BAD_RESIDUE) {
+        msv_vit_traces_free(t);
+        throw std::out_of_range("residue outside the 20 amino acids");
+    }
+    check(s, "msv_vit_trace_batch");
+    Viterbi_traces r;
+    r.scores.resize(msv_vit_traces_count(t));
+    r.domain_offsets.resize(r.scores.size() + 1);
+    r.domains.resize(msv_vit_traces_domains(t));
+    r.ops.resize(msv_vit_traces_ops(t));
+    msv_vit_traces_copy(t, r.scores.data(), r.domain_offsets.data(), r.domains.data(), r.ops.data());
+    msv_vit_traces_free(t);
+    return r;
+}
+
+Viterbi_traces Viterbi_HMM::trace_on_sequence(const Protein_sequence& seq) {
+    const size_t L = seq.empty() ? 0 : seq.size() - 1;
+    std::vector<uint8_t> codes(L);
+    if (L && msv_encode_residues(seq.data() + 1, L, codes.data()) != MSV_OK)
+        throw std::out_of_range("residue outside the 20 amino acids");
+    msv_host::VitTrace t = msv_host::viterbi_trace_on_sequence(
+        match_scores_.data(), inserts_ ? insert_scores_.data() : nullptr, transition_scores_.data(), model_length_,
+        tr_B_Mk_, tr_E_C_, tr_E_J_, codes.data(), L);
+    Viterbi_traces r;
+    r.scores = {t.score};
+    r.domain_offsets = {0, t.domains.size()};
+    r.domains = std::move(t.domains);
+    r.ops = std::move(t.ops);
+    return r;
+}
+
 Filter_result filter_pipeline(MSV_HMM& msv, Viterbi_HMM& vit, const Packed_sequences& packed, float msv_mu,
                               float msv_lambda, double F1) {
     Filter_result r;

@@ -22,6 +22,7 @@
 #include "msv.h"
 #include "msv_kernel.h"
 #include "vit_kernel.h"
+#include "vit_profile.h"
 
 using msvrt::csr_extent;
 using msvrt::DeviceBuffer;
@@ -34,18 +35,13 @@ static_assert(vitk::MM_IN == 0 && vitk::IM_IN == 1 && vitk::DM_IN == 2 && vitk::
                   vitk::MD_IN == 5 && vitk::DD_IN == 6,
               "table_layout.cpp's slot arrays");
 
-namespace {
+using vitdev::kErrWord;
+using vitdev::kHostErrWord;
+using vitdev::kSelWord;
+using vitdev::kWords;
+using vitdev::read_errors;
 
-constexpr uint32_t kDefaultMaxLength = 131072;
-// d_words: [2k, 2k+1] = launch slot k's dequeue counters {next index, leavers} (zero between launches),
-// [kErrWord] = sticky error bits of device launches (msv_vit_profile_check), [kHostErrWord] = the error bits
-// of the synchronous host calls, which report and clear only their own, [kSelWord] = msv_vit_filter_batch's
-// survivors count.
-constexpr int kLaunchSlots = 8;
-constexpr int kErrWord = 2 * kLaunchSlots;
-constexpr int kHostErrWord = kErrWord + 1;
-constexpr int kSelWord = kHostErrWord + 1;
-constexpr int kWords = kSelWord + 1;
+namespace vitdev {
 
 msv_status err_status(uint32_t err) {
     if (err & msvk::kErrBadResidue) return MSV_ERR_BAD_RESIDUE;
@@ -55,6 +51,11 @@ msv_status err_status(uint32_t err) {
     return err ? MSV_ERR_INVALID_ARGUMENT : MSV_OK;
 }
 
+}  // namespace vitdev
+
+namespace {
+
+constexpr uint32_t kDefaultMaxLength = 131072;
 // The automatic choice covering `states`: among the variants marked `pick` (one per S and insert mode, by
 // measurement), the fewest slots.  Informative insert scores need an isc variant.
 const vitk::VitVariant* pick_variant(uint32_t states, bool isc) {
@@ -68,36 +69,6 @@ const vitk::VitVariant* pick_variant(uint32_t states, bool isc) {
     }
     return best;
 }
-
-}  // namespace
-
-struct msv_vit_profile {
-    int device = 0;
-    uint32_t model_length = 0;  // LENG + 1
-    bool isc = false;
-    float tr_B_Mk = 0, tr_E_C = 0, tr_E_J = 0;
-    std::vector<float> msc, isc_tab, tsc;  // host copies (re-laid when the variant changes)
-    const vitk::VitVariant* v = nullptr;
-    uint32_t blocks = 0;                // persistent grid of a full launch
-    DeviceBuffer<float2> d_etab;        // [20][S/2][64]
-    DeviceBuffer<float2> d_itab;        // [20][S/2][64] (isc)
-    DeviceBuffer<float2> d_ttab;        // [7][S/2][64]
-    DeviceBuffer<float2> d_lentab;
-    uint32_t lentab_n = 0;
-    DeviceBuffer<uint32_t> d_words;     // kWords, see kLaunchSlots
-    msvrt::LaunchRing<kLaunchSlots> kernels;  // the launch slots' streams and events
-    msvrt::Stream stream;
-    hipStream_t bound = nullptr;        // msv_vit_profile_bind_stream: a caller stream kept alive while bound
-    // msv_vit_score_batch / msv_vit_filter_batch staging (staged.d_scores: the Viterbi scores); the filter's
-    // MSV scores and survivors list beside it
-    msvrt::CsrStaging staged;
-    DeviceBuffer<float> d_msc_out;
-    DeviceBuffer<uint32_t> d_sel;
-    hipEvent_t time_start = nullptr, time_stop = nullptr;  // msv_vit_debug_time_next_launch
-    uint64_t* d_stamps = nullptr;                          // msv_vit_debug_set_stamps (tools only)
-};
-
-namespace {
 
 // Lays the variant's tables out (msv_host::vit_tables) and uploads them, all three or none: each goes into a
 // fresh buffer, and the profile adopts them together.
@@ -173,6 +144,10 @@ msv_status launch(msv_vit_profile* p, const uint8_t* d_residues, const uint64_t*
     return MSV_OK;
 }
 
+}  // namespace
+
+namespace vitdev {
+
 // Reads (and clears when set) one error word of the profile on `st`, synchronously.
 msv_status read_errors(msv_vit_profile* p, int word, hipStream_t st) {
     uint32_t err = 0;
@@ -185,7 +160,7 @@ msv_status read_errors(msv_vit_profile* p, int word, hipStream_t st) {
     return err_status(err);
 }
 
-}  // namespace
+}  // namespace vitdev
 
 extern "C" {
 

@@ -411,6 +411,98 @@ msv_status msv_vit_filter_batch(msv_profile* msv, msv_vit_profile* vit, const ui
                                 const uint64_t* offsets, uint64_t n, float msv_mu, float msv_lambda, double F1,
                                 float* msv_scores, uint8_t* passed, float* vit_scores, uint64_t* n_passed);
 
+/* ---- Viterbi traces: one optimal state path per sequence ---------------------------
+ * The path runs through the model above: N, B, M/I/D of nodes 1..LENG, E, J, C.  It is reported as
+ * domains (one pass B -> M .. M -> E each, in sequence order) plus one op byte per core state visited,
+ * 'M' (i+1, k+1), 'I' (i+1) or 'D' (k+1) from (i_from, k_from); a domain's first and last op are 'M'.
+ * The specials follow: N loops up to the first domain, J between domains, C after the last.
+ * Ties (two predecessors giving the same float) are broken in a fixed order, so the CPU and the GPU
+ * report the SAME path: M takes M, I, D, B in that order; I takes M before I; D takes M before D; E the
+ * smallest k with M(i,k) == E(i); C and J the loop before E; B takes N before J.  The source of a cell is
+ * found by comparing its final value with fl(pred + t) of each candidate in that order.
+ * A sequence with L = 0 (score -inf), a bad residue (+inf) or too long for the profile (NaN) has no
+ * domains. */
+typedef struct msv_vit_domain {
+    uint32_t seq;                  /* index of the sequence in the batch                            */
+    uint32_t i_from, i_to;         /* 1-based residues emitted by the domain's first and last M     */
+    uint32_t k_from, k_to;         /* 1-based nodes of the first and last M                         */
+    uint32_t ops_len;              /* core states visited, first and last M included                */
+    uint64_t ops_begin;            /* index of the domain's first op in the ops bytes               */
+} msv_vit_domain;
+
+/* The serial CPU trace of one sequence (the DP of msv_vit_cpu_score with a pointer matrix, walked back):
+ * *score has msv_vit_cpu_score's bits.  Two calls size the output: with domains and ops NULL only the
+ * counts are written; then domains[*n_domains] (seq = 0, ops_begin from 0) and ops[*n_ops].  Transition
+ * scores of nodes 1 .. LENG-1 must be <= 0 (msv_vit_profile_create's rule). */
+msv_status msv_vit_cpu_trace(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                             uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                             uint64_t L, float* score, uint32_t* n_domains, uint64_t* n_ops, msv_vit_domain* domains,
+                             uint8_t* ops);
+
+/* The compiled trace plans, by rising capacity (states = LENG covered); a model runs the first that holds
+ * it.  Host-only. */
+int msv_vit_trace_plan_count(void);
+const char* msv_vit_trace_plan_name(int i);
+uint32_t msv_vit_trace_plan_capacity(int i);
+/* Back-pointer layout of a plan (host-only arithmetic shared by the device layer and the tests): a cell
+ * takes 4 bits (M source 2: 0 M, 1 I, 2 D, 3 B; I source 1: 0 M, 1 I; D source 1: 0 M, 1 D), eight cells
+ * a uint32, stored [row][word][lane].  Node k (1-based) of plan i lives in *word, *lane at bit *shift;
+ * *words and *lanes are the plan's row shape.  Any output may be NULL. */
+msv_status msv_vit_trace_plan_cell(int i, uint32_t k, uint32_t* word, uint32_t* lane, uint32_t* shift, uint32_t* words,
+                                   uint32_t* lanes);
+/* Workspace bytes of one sequence of L residues under plan i: L rows of words x lanes uint32 plus one
+ * uint32 record per row (E's argmax k | C from E << 16 | J from E << 17 | B from J << 18). */
+uint64_t msv_vit_trace_sequence_bytes(int i, uint64_t L);
+/* Cuts sequences of the given workspace sizes, in order, into chunks of at most workspace_bytes: chunk c
+ * is [cuts[c], cuts[c+1]), *n_chunks of them (cuts needs n + 1 entries; NULL: count only).  A sequence
+ * that alone exceeds the workspace gives MSV_ERR_OUT_OF_MEMORY. */
+msv_status msv_vit_trace_chunk_cuts(const uint64_t* bytes, uint64_t n, uint64_t workspace_bytes, uint64_t* cuts,
+                                    uint64_t* n_chunks);
+
+/* Traces of the selected sequences of a host batch, computed on the device (vit_trace.hip), synchronous.
+ * select NULL = every sequence (n_select ignored); an entry >= n gives MSV_ERR_INVALID_ARGUMENT.  Results
+ * are per select entry, in the caller's order (an index may repeat).  workspace_bytes bounds the device
+ * memory for back-pointers (0 = the default, 1 GiB): the selected sequences run in chunks that fit it, and
+ * a sequence that alone exceeds it gives MSV_ERR_OUT_OF_MEMORY before anything is launched.
+ * MSV_ERR_BAD_RESIDUE / MSV_ERR_SEQUENCE_TOO_LONG are reported as msv_vit_score_batch reports them, and
+ * *traces is still returned: the offending entries have no domains, the others are traced. */
+typedef struct msv_vit_traces msv_vit_traces;
+msv_status msv_vit_trace_batch(msv_vit_profile* profile, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                               const uint32_t* select, uint64_t n_select, uint64_t workspace_bytes,
+                               msv_vit_traces** traces);
+uint64_t msv_vit_traces_count(const msv_vit_traces* traces);      /* select entries */
+uint64_t msv_vit_traces_domains(const msv_vit_traces* traces);    /* domains in all */
+uint64_t msv_vit_traces_ops(const msv_vit_traces* traces);        /* op bytes in all */
+/* scores[count], domain_offsets[count + 1] (entry q's domains are [q], [q+1]), domains[], ops[]; any may
+ * be NULL. */
+msv_status msv_vit_traces_copy(const msv_vit_traces* traces, float* scores, uint64_t* domain_offsets,
+                               msv_vit_domain* domains, uint8_t* ops);
+void msv_vit_traces_free(msv_vit_traces* traces);
+
+typedef struct msv_vit_trace_info {
+    char plan[64];
+    uint32_t states_per_lane;
+    uint32_t lanes_per_sequence;   /* 64 x the waves of the sequence's workgroup                    */
+    uint32_t capacity;             /* states                                                        */
+    uint32_t scratch_bytes;        /* of the fill kernel (hipFuncGetAttributes)                     */
+    uint32_t words_per_lane;       /* uint32 of back-pointers per lane and row                      */
+    uint32_t blocks;               /* resident workgroups = sequences in flight of a full launch    */
+    uint32_t lds_bytes;
+    uint32_t reserved;
+    uint64_t default_workspace_bytes;
+} msv_vit_trace_info;
+/* The trace plan this profile's model runs. */
+msv_status msv_vit_trace_describe(msv_vit_profile* profile, msv_vit_trace_info* out);
+
+/* What the call that made `traces` did on the device: its chunks, the back-pointer bytes written, and the
+ * summed device times of the fill launches and of the two walk launches (HIP events). */
+typedef struct msv_vit_trace_stats {
+    uint64_t chunks;
+    uint64_t pointer_bytes;
+    float fill_ms, walk_ms;
+} msv_vit_trace_stats;
+msv_status msv_vit_traces_stats(const msv_vit_traces* traces, msv_vit_trace_stats* out);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

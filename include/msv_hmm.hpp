@@ -160,6 +160,16 @@ class MSV_HMM::Multi_device {
 // the reference's parse -- insert emissions and the 7 transitions per node -- with the MSV path's specials.
 // Same shape as MSV_HMM: run_on_sequence is this library's serial CPU DP, parallel_run_on_sequence and
 // score_batch the gfx950 kernel (bit-identical to each other).  STATS LOCAL VITERBI gives the P-values.
+// One optimal state path per traced sequence (msv.h "Viterbi traces"): entry q's domains are
+// domains[domain_offsets[q] .. domain_offsets[q + 1]), a domain's ops are ops[ops_begin .. ops_begin + ops_len).
+struct Viterbi_traces {
+    std::vector<Log_score> scores;
+    std::vector<uint64_t> domain_offsets{0};
+    std::vector<msv_vit_domain> domains;
+    std::vector<uint8_t> ops;
+    size_t size() const { return scores.size(); }
+};
+
 class Viterbi_HMM {
   public:
     explicit Viterbi_HMM(const Profile_HMM& base_hmm, int device = 0, msv_insert_mode inserts = MSV_INSERTS_ZERO);
@@ -173,6 +183,11 @@ class Viterbi_HMM {
     Log_score parallel_run_on_sequence(const Protein_sequence& seq);
     std::vector<Log_score> score_batch(const Protein_sequences& seqs);
     std::vector<Log_score> score_batch(const Packed_sequences& packed);
+    // Traces of the selected sequences (every sequence when `select` is empty and `all` is set), computed on the
+    // GPU (msv_vit_trace_batch); trace_on_sequence is the serial CPU trace (msv_vit_cpu_trace), the same path.
+    Viterbi_traces trace_batch(const Packed_sequences& packed, const std::vector<uint32_t>& select = {},
+                               bool all = true, uint64_t workspace_bytes = 0);
+    Viterbi_traces trace_on_sequence(const Protein_sequence& seq);
 
     msv_vit_profile* handle() { return profile_; }
     size_t model_length() const { return model_length_; }

@@ -14,4 +14,5 @@ done
 /opt/rocm/bin/hipcc $FLAGS "$HERE/msv_coop.hip" -o "$OUT/msv_coop.s" &
 /opt/rocm/bin/hipcc $FLAGS "$HERE/vit_kernel.hip" -o "$OUT/vit_kernel.s" &
 /opt/rocm/bin/hipcc $FLAGS "$HERE/vit_team.hip" -o "$OUT/vit_team.s" &
+/opt/rocm/bin/hipcc $FLAGS "$HERE/vit_trace.hip" -o "$OUT/vit_trace.s" &
 wait
