@@ -10,6 +10,8 @@ Python mirror of the reference's C++ class surface, bound to libmsv_hip.so (incl
     Viterbi_HMM(profile)                    (new, SURVEY 8(f)-4: the Viterbi stage over the parse the
                                              reference never scores with, Profile_HMM.cpp:107-120)
     filter_pipeline(msv, vit, ...)          MSV -> P-value -> F1 -> Viterbi on the survivors, on the GPU
+    Forward_HMM(profile)                    (new, DESIGN 4.9: the summed odds of every alignment, with P-values)
+    search_pipeline(msv, vit, fwd, ...)     MSV -> F1 -> Viterbi -> F2 -> Forward -> P-value, on the GPU
 
 Sequences use the reference's form ('#' sentinel + one-letter residues) or packed codes
 0..19 (alphabetical A C D E F G H I K L M N P Q R S T V W Y) with CSR offsets.
@@ -29,7 +31,7 @@ __all__ = [
     "AMINO_ACIDS", "MSVError", "Profile_HMM", "FASTA_protein_sequences", "MSV_HMM", "pack_sequences",
     "encode", "sequence_transitions", "device_count", "score_grid", "score_grid_device", "score_batch_multi",
     "shard_bounds", "FASTA_device", "MultiGPU", "Viterbi_HMM", "filter_pipeline", "INSERTS_ZERO",
-    "INSERTS_LOG_ODDS", "Traces",
+    "INSERTS_LOG_ODDS", "Traces", "Forward_HMM", "search_pipeline",
 ]
 
 INSERTS_ZERO = 0      # HMMER3's insert scores (background emissions: 0)
@@ -642,6 +644,174 @@ def filter_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, seqs: Sequence
         traces = vit_engine.trace_batch(codes=codes, offsets=offsets, select=np.flatnonzero(mask).astype(np.uint32))
         return msc, mask, vsc, vpv, traces
     return msc, mask, vsc, vpv
+
+
+class Forward_HMM:
+    """Forward stage for one profile on one GPU (msv.h "Forward stage"): the log, in nats, of the summed
+    odds of EVERY alignment -- the score HMMER3's E-values come from.  Same tables and specials as Viterbi_HMM, plus
+    the D_k -> E exits.  Every score comes from the gfx950 kernel (fwd_kernel.hip, float32 odds with exact
+    power-of-two rescaling) except run_on_sequence, the library's serial float64 CPU Forward, which every test
+    compares against.  P-values use STATS LOCAL FORWARD."""
+
+    def __init__(self, base_hmm: Profile_HMM, device: int = 0, insert_mode: int = INSERTS_ZERO):
+        L = _native.lib()
+        M = base_hmm.model_length
+        self.model_length = M
+        self.insert_mode = insert_mode
+        self.match_scores = np.zeros((20, M), np.float32)
+        self.insert_scores = np.zeros((20, M), np.float32)
+        self.transition_scores = np.zeros((M, 7), np.float32)
+        b, c, j = C.c_float(), C.c_float(), C.c_float()
+        check(L.msv_hmm_viterbi_scores(base_hmm._h, insert_mode, self.match_scores.ctypes.data,
+                                       self.insert_scores.ctypes.data, self.transition_scores.ctypes.data,
+                                       C.byref(b), C.byref(c), C.byref(j)), "msv_hmm_viterbi_scores")
+        self.tr_B_Mk, self.tr_E_C, self.tr_E_J = b.value, c.value, j.value
+        p = C.c_void_p()
+        check(L.msv_fwd_profile_create(device, self.match_scores.ctypes.data,
+                                       self.insert_scores.ctypes.data if insert_mode == INSERTS_LOG_ODDS else None,
+                                       self.transition_scores.ctypes.data, M, self.tr_B_Mk, self.tr_E_C, self.tr_E_J,
+                                       C.byref(p)), "msv_fwd_profile_create")
+        self._p = p
+        self.device = device
+        self.forward_tau = base_hmm.stats_local_forward_theta
+        self.forward_lambda = base_hmm.stats_local_forward_lambda
+
+    def _tables(self):
+        return (self.match_scores.ctypes.data, self.insert_scores.ctypes.data if self.insert_mode else None,
+                self.transition_scores.ctypes.data, self.model_length, self.tr_B_Mk, self.tr_E_C, self.tr_E_J)
+
+    def run_on_sequence(self, seq: str) -> float:
+        """The serial float64 CPU Forward (msv_fwd_cpu_score); IndexError on a residue outside the 20."""
+        codes = encode(seq[1:] if seq.startswith("#") else seq)
+        out = C.c_double()
+        check(_native.lib().msv_fwd_cpu_score(*self._tables(), codes.ctypes.data if codes.size else None,
+                                              codes.size, C.byref(out)), "msv_fwd_cpu_score")
+        return out.value
+
+    def cpu_score_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
+                        offsets: np.ndarray | None = None) -> np.ndarray:
+        """run_on_sequence over a host batch (msv_fwd_cpu_score_batch, a few host threads) -> float64 [n]."""
+        if seqs is not None:
+            codes, offsets = pack_sequences(seqs)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        out = np.zeros(n, np.float64)
+        st = _native.lib().msv_fwd_cpu_score_batch(*self._tables(), codes.ctypes.data if codes.size else None,
+                                                   offsets.ctypes.data, n, out.ctypes.data)
+        if st == _native.MSV_ERR_BAD_RESIDUE:
+            raise IndexError("residue outside the 20 amino acids")
+        check(st, "msv_fwd_cpu_score_batch")
+        return out
+
+    def parallel_run_on_sequence(self, seq: str) -> float:
+        return float(self.score_batch([seq])[0])
+
+    def score_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
+                    offsets: np.ndarray | None = None) -> np.ndarray:
+        """Forward scores of every sequence of a host batch (msv_fwd_score_batch, one launch)."""
+        if seqs is not None:
+            codes, offsets = pack_sequences(seqs)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        out = np.zeros(n, np.float32)
+        st = _native.lib().msv_fwd_score_batch(self._p, codes.ctypes.data if codes.size else None,
+                                               offsets.ctypes.data, n, out.ctypes.data, None)
+        if st == _native.MSV_ERR_BAD_RESIDUE:
+            raise IndexError("residue outside the 20 amino acids")
+        check(st, "msv_fwd_score_batch")
+        return out
+
+    def score_batch_device(self, residues_ptr: int, residues_len: int, offsets_ptr: int, n: int, scores_ptr: int,
+                           select_ptr: int | None = None, select_count_ptr: int | None = None,
+                           stream: int | None = None) -> None:
+        """Device-resident batch (raw device pointers), optionally only the sequences listed at select_ptr
+        (uint32; their count in the device uint32 at select_count_ptr, else n); async on `stream`."""
+        check(_native.lib().msv_fwd_score_batch_device(self._p, residues_ptr, residues_len, offsets_ptr, n,
+                                                       select_ptr, select_count_ptr, scores_ptr, stream),
+              "msv_fwd_score_batch_device")
+
+    def reserve_length(self, max_length: int) -> None:
+        check(_native.lib().msv_fwd_profile_reserve_length(self._p, max_length))
+
+    def bind_stream(self, stream: int | None) -> None:
+        check(_native.lib().msv_fwd_profile_bind_stream(self._p, stream), "msv_fwd_profile_bind_stream")
+
+    def check(self, stream: int | None = None) -> None:
+        st = _native.lib().msv_fwd_profile_check(self._p, stream)
+        if st == _native.MSV_ERR_BAD_RESIDUE:
+            raise IndexError("residue outside the 20 amino acids")
+        check(st, "msv_fwd_profile_check")
+
+    def pvalues(self, scores: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+        """P-values of Forward scores against STATS LOCAL FORWARD (msv_fwd_pvalues)."""
+        scores = np.ascontiguousarray(scores, np.float32)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        if scores.shape != (n,):
+            raise ValueError("scores and offsets disagree")
+        out = np.zeros(n, np.float64)
+        check(_native.lib().msv_fwd_pvalues(scores.ctypes.data, offsets.ctypes.data, n, self.forward_tau,
+                                            self.forward_lambda, out.ctypes.data), "msv_fwd_pvalues")
+        return out
+
+    def pvalues_device(self, scores_ptr: int, offsets_ptr: int, n: int, pvalues_ptr: int,
+                       stream: int | None = None) -> None:
+        """Device P-values (float64 out) for device scores/offsets, async on `stream`."""
+        check(_native.lib().msv_fwd_pvalues_device(self.device, scores_ptr, offsets_ptr, n, self.forward_tau,
+                                                   self.forward_lambda, pvalues_ptr, stream), "msv_fwd_pvalues_device")
+
+    def set_variant(self, name: str) -> None:
+        check(_native.lib().msv_fwd_profile_set_variant(self._p, name.encode()), f"set_variant({name})")
+
+    @staticmethod
+    def variants() -> list[str]:
+        L = _native.lib()
+        return [L.msv_fwd_variant_name(i).decode() for i in range(L.msv_fwd_variant_count())]
+
+    def describe(self) -> dict:
+        info = _native.FwdInfo()
+        check(_native.lib().msv_fwd_profile_describe(self._p, C.byref(info)))
+        return info.as_dict()
+
+    def close(self):
+        lib = _loaded_lib()
+        if getattr(self, "_p", None) and lib is not None:
+            lib.msv_fwd_profile_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
+
+
+def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Forward_HMM,
+                    seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
+                    offsets: np.ndarray | None = None, F1: float = 0.02, F2: float = 1e-3) -> dict:
+    """HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV over every sequence, P <= F1, Viterbi on the
+    survivors, P <= F2, Forward on those, Forward P-values.  Returns the per-stage arrays: msv_scores, passed_msv,
+    vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run)."""
+    if seqs is not None:
+        codes, offsets = pack_sequences(seqs)
+    codes = np.ascontiguousarray(codes, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    n = len(offsets) - 1
+    stats = np.array([msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
+                      fwd_engine.forward_tau, fwd_engine.forward_lambda], np.float32)
+    msc, vsc, fsc = (np.zeros(n, np.float32) for _ in range(3))
+    p1, p2 = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    fpv = np.zeros(n, np.float64)
+    n1, n2 = C.c_uint64(0), C.c_uint64(0)
+    st = _native.lib().msv_fwd_filter_batch(msv_engine._p, vit_engine._p, fwd_engine._p,
+                                            codes.ctypes.data if codes.size else None, offsets.ctypes.data, n,
+                                            stats.ctypes.data, F1, F2, msc.ctypes.data, p1.ctypes.data,
+                                            vsc.ctypes.data, p2.ctypes.data, fsc.ctypes.data, fpv.ctypes.data,
+                                            C.byref(n1), C.byref(n2))
+    if st == _native.MSV_ERR_BAD_RESIDUE:
+        raise IndexError("residue outside the 20 amino acids")
+    check(st, "msv_fwd_filter_batch")
+    return {"msv_scores": msc, "passed_msv": p1.astype(bool), "vit_scores": vsc, "passed_vit": p2.astype(bool),
+            "fwd_scores": fsc, "fwd_pvalues": fpv}
 
 
 def _handles(engines: Sequence[MSV_HMM]):

@@ -58,6 +58,11 @@ EXPORTED = [
     "msv_vit_trace_plan_cell", "msv_vit_trace_sequence_bytes", "msv_vit_trace_chunk_cuts", "msv_vit_trace_batch",
     "msv_vit_traces_count", "msv_vit_traces_domains", "msv_vit_traces_ops", "msv_vit_traces_copy",
     "msv_vit_traces_free", "msv_vit_trace_describe", "msv_vit_traces_stats",
+    "msv_fwd_cpu_score", "msv_fwd_cpu_score_batch", "msv_fwd_pvalues", "msv_fwd_scan_constants",
+    "msv_fwd_profile_create", "msv_fwd_profile_create_from_hmm", "msv_fwd_profile_destroy",
+    "msv_fwd_profile_reserve_length", "msv_fwd_profile_describe", "msv_fwd_variant_count", "msv_fwd_variant_name",
+    "msv_fwd_profile_set_variant", "msv_fwd_score_batch_device", "msv_fwd_profile_bind_stream",
+    "msv_fwd_score_batch", "msv_fwd_profile_check", "msv_fwd_pvalues_device", "msv_fwd_filter_batch",
 ]
 
 
@@ -115,6 +120,27 @@ class VitInfo(C.Structure):
         ("variant", C.c_char * 64),
         ("scratch_bytes", C.c_uint32),
         ("waves_per_sequence", C.c_uint32),
+    ]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["variant"] = self.variant.decode()
+        return d
+
+
+class FwdInfo(C.Structure):
+    _fields_ = [
+        ("model_length", C.c_uint32),
+        ("states_per_lane", C.c_uint32),
+        ("match_in_lds", C.c_uint32),
+        ("insert_scores", C.c_uint32),
+        ("waves_per_block", C.c_uint32),
+        ("blocks", C.c_uint32),
+        ("lds_bytes", C.c_uint32),
+        ("scratch_bytes", C.c_uint32),
+        ("max_length", C.c_uint32),
+        ("device", C.c_int),
+        ("variant", C.c_char * 64),
     ]
 
     def as_dict(self) -> dict:
@@ -282,6 +308,25 @@ def lib() -> C.CDLL:
         "msv_vit_traces_free": (None, [vp]),
         "msv_vit_trace_describe": (C.c_int, [vp, C.POINTER(VitTraceInfo)]),
         "msv_vit_traces_stats": (C.c_int, [vp, C.POINTER(VitTraceStats)]),
+        "msv_fwd_cpu_score": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, u64, C.POINTER(C.c_double)]),
+        "msv_fwd_cpu_score_batch": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, vp, u64, vp]),
+        "msv_fwd_pvalues": (C.c_int, [vp, vp, u64, f32, f32, vp]),
+        "msv_fwd_scan_constants": (C.c_int, [vp, u32, u32, vp, vp, vp]),
+        "msv_fwd_profile_create": (C.c_int, [C.c_int, vp, vp, vp, u32, f32, f32, f32, C.POINTER(vp)]),
+        "msv_fwd_profile_create_from_hmm": (C.c_int, [C.c_int, vp, C.c_int, C.POINTER(vp)]),
+        "msv_fwd_profile_destroy": (None, [vp]),
+        "msv_fwd_profile_reserve_length": (C.c_int, [vp, u64]),
+        "msv_fwd_profile_describe": (C.c_int, [vp, C.POINTER(FwdInfo)]),
+        "msv_fwd_variant_count": (C.c_int, []),
+        "msv_fwd_variant_name": (C.c_char_p, [C.c_int]),
+        "msv_fwd_profile_set_variant": (C.c_int, [vp, C.c_char_p]),
+        "msv_fwd_score_batch_device": (C.c_int, [vp, vp, u64, vp, u64, vp, vp, vp, vp]),
+        "msv_fwd_profile_bind_stream": (C.c_int, [vp, vp]),
+        "msv_fwd_score_batch": (C.c_int, [vp, vp, vp, u64, vp, vp]),
+        "msv_fwd_profile_check": (C.c_int, [vp, vp]),
+        "msv_fwd_pvalues_device": (C.c_int, [C.c_int, vp, vp, u64, f32, f32, vp, vp]),
+        "msv_fwd_filter_batch": (C.c_int, [vp, vp, vp, vp, vp, u64, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp,
+                                           vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

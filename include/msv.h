@@ -503,6 +503,106 @@ typedef struct msv_vit_trace_stats {
 } msv_vit_trace_stats;
 msv_status msv_vit_traces_stats(const msv_vit_traces* traces, msv_vit_trace_stats* out);
 
+/* ---- Forward stage: the summed odds of every alignment, and its P-value -------------
+ * The score that decides whether a sequence is a hit: the log (nats) of the sum over EVERY state path of
+ * the path's odds, where the Viterbi stage takes the best path only.  Tables and specials are the Viterbi
+ * stage's (msv_hmm_viterbi_scores, msv_sequence_transitions); the paths are the Viterbi stage's plus ONE
+ * addition: D_k -> E is a local exit at no cost for k = 2..LENG, as in HMMER3's p7_GForward (a max never
+ * takes these paths, a sum must count them: STATS LOCAL FORWARD was calibrated with them counted).
+ * With x = exp(score) for every table entry (-inf and padding give 0), row i, residue r:
+ *   M(i,k) = m[r][k] * (M(i-1,k-1) tMM[k-1] + I(i-1,k-1) tIM[k-1] + D(i-1,k-1) tDM[k-1] + B(i-1) tBM)
+ *   I(i,k) = ins[r][k] * (M(i-1,k) tMI[k] + I(i-1,k) tII[k])              k = 1..LENG-1
+ *   D(i,k) = M(i,k-1) tMD[k-1] + D(i,k-1) tDD[k-1]                        k = 2..LENG
+ *   E(i) = sum_k M(i,k) + sum_{k>=2} D(i,k)
+ *   N(i) = N(i-1) loop;  J(i) = J(i-1) loop + E(i) tEJ;  C(i) = C(i-1) loop + E(i) tEC;  B(i) = (N(i) + J(i)) move
+ *   N(0) = 1, everything else 0 at row 0;  score = log(C(L) move)
+ * The CPU function runs this serially in float64 (tables exp((double)float_score)) and is the reference of
+ * every test.  The device computes float32 odds rescaled by exact powers of two; for every finite score
+ *   |gpu - cpu64| <= 16 (L + LENG) 2^-24 + 4 2^-24 |cpu64|  nats
+ * (DESIGN 4.9 derives it).  A sequence's device score is deterministic: it does not depend on the
+ * sequence's place in the batch, on the select list, on the stream or on the run.  Unlike the Viterbi
+ * stage's, the variants do NOT return identical scores: S changes the order of summation, so two variants
+ * may differ within the tolerance.
+ * P-value (HMMER3): bits = (score - nullsc) / ln 2 with msv_pvalues' null1 nullsc; P = 1 when bits < tau,
+ * else exp(-lambda (bits - tau)); tau, lambda = STATS LOCAL FORWARD (msv_hmm_stats slots 4 and 5).  The
+ * null2 / bias corrections, Backward, posterior decoding and domain envelopes are not part of this stage. */
+typedef struct msv_fwd_profile msv_fwd_profile;
+
+/* The serial float64 CPU Forward of one sequence, arguments as msv_vit_cpu_score.  L = 0 scores -inf; a code
+ * >= 20 gives MSV_ERR_BAD_RESIDUE.  The batch form scores a CSR batch on a few host threads. */
+msv_status msv_fwd_cpu_score(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                             uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                             uint64_t L, double* score);
+msv_status msv_fwd_cpu_score_batch(const float* match_scores, const float* insert_scores,
+                                   const float* transition_scores, uint32_t model_length, float tr_B_Mk, float tr_E_C,
+                                   float tr_E_J, const uint8_t* codes, const uint64_t* offsets, uint64_t n,
+                                   double* scores);
+/* Forward P-values on the host (the formula above). */
+msv_status msv_fwd_pvalues(const float* scores, const uint64_t* offsets, uint64_t n, float tau, float lambda,
+                           double* pvalues);
+/* The D-scan constants of a variant of states_per_lane = S states per lane (host-only, what the device layer
+ * uploads): per lane l and slot q (state l S + q + 1), slot_dd[l S + q] = the float32 odds of the d->d
+ * transition into the slot (0 where none) and slot_prefix[l S + q] = c_q, the product of the lane's slot_dd
+ * 0..q; step_products[j * 64 + l] = step j's multiplier of lane l, the product of the whole-lane products
+ * c_{S-1} of lanes max(0, l - 2^j + 1) .. l (j = 0..5).  Any output may be NULL. */
+msv_status msv_fwd_scan_constants(const float* transition_scores, uint32_t model_length, uint32_t states_per_lane,
+                                  float* slot_dd, float* slot_prefix, float* step_products);
+
+/* Device-resident Forward profile; arguments, threading and streams as msv_vit_profile_create.  The compiled
+ * variants cover LENG <= 2432 (all bundled profiles); beyond, MSV_ERR_UNSUPPORTED_MODEL. */
+msv_status msv_fwd_profile_create(int device, const float* match_scores, const float* insert_scores,
+                                  const float* transition_scores, uint32_t model_length, float tr_B_Mk, float tr_E_C,
+                                  float tr_E_J, msv_fwd_profile** out);
+msv_status msv_fwd_profile_create_from_hmm(int device, const msv_hmm* hmm, int insert_mode, msv_fwd_profile** out);
+void msv_fwd_profile_destroy(msv_fwd_profile* profile);
+msv_status msv_fwd_profile_reserve_length(msv_fwd_profile* profile, uint64_t max_length);
+
+typedef struct msv_fwd_info {
+    uint32_t model_length;    /* LENG + 1                                                   */
+    uint32_t states_per_lane; /* S: one sequence per 64-lane wave, 64 * S >= LENG             */
+    uint32_t match_in_lds;    /* match odds staged in LDS (else read from L2 every row)      */
+    uint32_t insert_scores;   /* informative insert odds (read from L2)                      */
+    uint32_t waves_per_block;
+    uint32_t blocks;          /* persistent grid of a full launch                           */
+    uint32_t lds_bytes;
+    uint32_t scratch_bytes;   /* private memory per lane of the variant's kernel (0: no spills) */
+    uint32_t max_length;
+    int device;
+    char variant[64];
+} msv_fwd_info;
+msv_status msv_fwd_profile_describe(const msv_fwd_profile* profile, msv_fwd_info* out);
+int msv_fwd_variant_count(void);
+const char* msv_fwd_variant_name(int i);
+/* Force one compiled variant (tuning / tests).  Variants may differ within the tolerance above. */
+msv_status msv_fwd_profile_set_variant(msv_fwd_profile* profile, const char* name);
+
+/* As msv_vit_score_batch_device: d_select / d_select_count choose the sequences, scores are written at the
+ * sequence's index (others untouched).  An empty sequence scores -inf; a bad residue (+inf), a sequence too
+ * long for the profile (NaN), a d_select entry >= n (skipped) and a count beyond n (clamped) are latched for
+ * msv_fwd_profile_check. */
+msv_status msv_fwd_score_batch_device(msv_fwd_profile* profile, const uint8_t* d_residues, uint64_t residues_len,
+                                      const uint64_t* d_offsets, uint64_t n, const uint32_t* d_select,
+                                      const uint32_t* d_select_count, float* d_scores, void* stream);
+msv_status msv_fwd_profile_bind_stream(msv_fwd_profile* profile, void* stream);
+/* Host buffers in and out, synchronous (every sequence scored); reports only its own errors. */
+msv_status msv_fwd_score_batch(msv_fwd_profile* profile, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                               float* scores, void* stream);
+msv_status msv_fwd_profile_check(msv_fwd_profile* profile, void* stream);
+msv_status msv_fwd_pvalues_device(int device, const float* d_scores, const uint64_t* d_offsets, uint64_t n, float tau,
+                                  float lambda, double* d_pvalues, void* stream);
+
+/* The full cascade on host buffers: MSV over every sequence; P <= F1 (stats[0..1], STATS LOCAL MSV); Viterbi
+ * on those; P <= F2 (stats[2..3], STATS LOCAL VITERBI); Forward on those; Forward P-values (stats[4..5],
+ * STATS LOCAL FORWARD) -- `stats` is msv_hmm_stats' six floats.  Written: msv_scores[n], passed_msv[n] (0/1),
+ * vit_scores[n] (-inf where not run), passed_vit[n], fwd_scores[n] (-inf where not run), fwd_pvalues[n]
+ * (1 where not run) and the two survivor counts.  Everything between the upload and the download stays on
+ * the device; the three profiles must live on one device. */
+msv_status msv_fwd_filter_batch(msv_profile* msv, msv_vit_profile* vit, msv_fwd_profile* fwd, const uint8_t* residues,
+                                const uint64_t* offsets, uint64_t n, const float* stats, double F1, double F2,
+                                float* msv_scores, uint8_t* passed_msv, float* vit_scores, uint8_t* passed_vit,
+                                float* fwd_scores, double* fwd_pvalues, uint64_t* n_passed_msv,
+                                uint64_t* n_passed_vit);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -212,3 +212,43 @@ struct Filter_result {
 };
 Filter_result filter_pipeline(MSV_HMM& msv, Viterbi_HMM& vit, const Packed_sequences& packed, float msv_mu,
                               float msv_lambda, double F1 = 0.02);
+
+// The Forward stage (msv.h "Forward stage"): the log of the summed odds of every alignment, in nats.
+// run_on_sequence is the library's serial float64 CPU Forward, the reference of every test;
+// parallel_run_on_sequence and score_batch the gfx950 kernel (float32 odds, within msv.h's tolerance of it).
+// STATS LOCAL FORWARD gives the P-values.
+class Forward_HMM {
+  public:
+    explicit Forward_HMM(const Profile_HMM& base_hmm, int device = 0, msv_insert_mode inserts = MSV_INSERTS_ZERO);
+    ~Forward_HMM();
+    Forward_HMM(const Forward_HMM&) = delete;
+    Forward_HMM& operator=(const Forward_HMM&) = delete;
+
+    double run_on_sequence(const Protein_sequence& seq);
+    Log_score parallel_run_on_sequence(const Protein_sequence& seq);
+    std::vector<Log_score> score_batch(const Protein_sequences& seqs);
+    std::vector<Log_score> score_batch(const Packed_sequences& packed);
+    std::vector<double> pvalues(const std::vector<Log_score>& scores, const Packed_sequences& packed) const;
+
+    msv_fwd_profile* handle() { return profile_; }
+    size_t model_length() const { return model_length_; }
+    float forward_tau = 0, forward_lambda = 0;  // STATS LOCAL FORWARD
+
+  private:
+    size_t model_length_ = 0;
+    bool inserts_ = false;
+    std::vector<float> match_scores_, insert_scores_, transition_scores_;  // [20][M], [20][M], [M][7]
+    float tr_B_Mk_ = 0, tr_E_C_ = 0, tr_E_J_ = 0;
+    msv_fwd_profile* profile_ = nullptr;
+};
+
+// HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV -> P <= F1 -> Viterbi -> P <= F2 -> Forward ->
+// P-value, with the six STATS values of the profile (msv mu, lambda, viterbi mu, lambda, forward tau, lambda).
+struct Search_result {
+    std::vector<Log_score> msv_scores, viterbi_scores, forward_scores;  // -inf where a stage did not run
+    std::vector<uint8_t> passed_msv, passed_viterbi;
+    std::vector<double> forward_pvalues;
+    size_t n_passed_msv = 0, n_passed_viterbi = 0;
+};
+Search_result search_pipeline(MSV_HMM& msv, Viterbi_HMM& vit, Forward_HMM& fwd, const Packed_sequences& packed,
+                              const Profile_HMM& stats, double F1 = 0.02, double F2 = 1e-3);
