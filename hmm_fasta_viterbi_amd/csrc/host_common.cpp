@@ -148,6 +148,13 @@ msv_status msv_shard_bounds(const uint64_t* offsets, uint64_t n, uint32_t n_shar
     return MSV_OK;
 }
 
+msv_status msv_lazy_bound_table(const float* emission_scores, uint32_t model_length, int G, int S, float* out) {
+    if (!emission_scores || !out || model_length < 2 || G <= 0 || S <= 0) return MSV_ERR_INVALID_ARGUMENT;
+    const std::vector<float> tab = msv_host::msv_lazy_bound_table(emission_scores, model_length, G, S);
+    std::copy(tab.begin(), tab.end(), out);
+    return MSV_OK;
+}
+
 }  // extern "C"
 
 namespace msv_host {

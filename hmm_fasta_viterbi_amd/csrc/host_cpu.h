@@ -33,6 +33,9 @@ VitTrace viterbi_trace_on_sequence(const float* msc, const float* isc, const flo
 // residue-major host tables.  The device layer uploads them as they are.
 // An MSV variant of G lanes per sequence, S states per lane, the first sa of them in LDS (0: the whole row).
 std::vector<float> msv_variant_table(const float* es, uint32_t model_length, int G, int S, int sa);
+// The lazy-E bound of a whole-row variant: [21][G] per-lane emission maxima (poison row +inf); the device
+// layer appends it to the table of the variants whose kernel skips idle E maxima (msvk::lazy_e_rows).
+std::vector<float> msv_lazy_bound_table(const float* es, uint32_t model_length, int G, int S);
 // A cooperative MSV variant of `waves` waves of 64 lanes x S states, neighbours sharing `halo` states.
 std::vector<float> msv_coop_table(const float* es, uint32_t model_length, int waves, int S, int sa, int halo);
 // A Viterbi variant of S states per lane and `team` waves per sequence: match, insert (empty unless isc)

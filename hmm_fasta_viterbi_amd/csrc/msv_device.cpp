@@ -217,8 +217,13 @@ static msv_status grid_blocks(int device, const void* kernel, int waves, int* bl
 
 // Lays the MSV table out for variant v (msv_host::msv_variant_table), uploads it and sizes the grid.
 static msv_status install_plan(msv_profile* p, const msvk::Variant* v, Plan& plan) {
-    const std::vector<float> tab =
+    std::vector<float> tab =
         msv_host::msv_variant_table(p->emission_scores.data(), p->model_length, v->G, v->S, v->sa);
+    if (msvk::lazy_e_rows(v->S, v->waves, v->pf, v->big, v->sa, v->streams)) {  // the kernel stages the bound table behind the rows
+        const std::vector<float> emax =
+            msv_host::msv_lazy_bound_table(p->emission_scores.data(), p->model_length, v->G, v->S);
+        tab.insert(tab.end(), emax.begin(), emax.end());
+    }
     // (the old table may be read by an in-flight launch on any stream the caller used: replace_with)
     MSV_HIP(plan.d_etab.replace_with(reinterpret_cast<const float4*>(tab.data()), tab.size() / 4));
     plan.v = v;

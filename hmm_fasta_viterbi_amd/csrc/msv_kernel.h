@@ -32,6 +32,18 @@ constexpr int lds_rows_for(int G, int S) {
     return (kLdsLimit / (G * S * 4)) >= kTableRows ? kTableRows : (kLdsLimit / (G * S * 4));
 }
 
+// Variants whose rows skip the E maximum where a per-lane bound proves it idle (msv_kernel_body.inc, LAZY):
+// the whole-row, one-stream rows of 68 states and more at 16 waves per workgroup (4 per SIMD) and a two-chunk
+// ring -- the 16-lane throughput plans of 1025-1408 states.  Measured per plan, parent against branch
+// (profiles/r08_ab_lazy_e.md): 68-88 states per lane gain 0.6-3.1%; 64 states (the bound's fixed cost against a
+// shorter E block) and the 12-wave plans of 92 / 96 states (3 waves per SIMD: less cover for the bound's
+// LDS read -> compare -> branch chain at the row start) lose 1.9-3.5% and keep their rows.
+// A lazy variant's table is followed, in the same buffer, by the bound table [21][G] floats
+// (msv_host::msv_lazy_bound_table), which the kernel stages in LDS behind it.
+constexpr bool lazy_e_rows(int S, int waves, int pf, bool big, int sa, int streams) {
+    return !big && sa == 0 && streams == 1 && S >= 68 && waves == 16 && pf == 2;
+}
+
 // MSV filter P-value of one score (HMMER3's MSV-stage formula, msv.h msv_pvalues): used by the P-value
 // kernel, the host path and the Viterbi stage's survivor selection (vit_kernel.hip).
 __device__ __host__ inline double msv_pvalue_of(float score, uint64_t L, float mu, float lambda) {
@@ -47,6 +59,7 @@ __device__ __host__ inline double msv_pvalue_of(float score, uint64_t L, float m
 
 struct KernelArgs {
     const float4* etab;        // [21][S/4][G] float4, global copy of the kernel-layout table
+                               // (lazy_e_rows variants: then [21][G] floats, the lazy-E bound table)
     const uint8_t* residues;   // CSR residue codes
     const uint64_t* offsets;   // n + 1
     const uint32_t* order;     // optional dequeue permutation (n) or nullptr

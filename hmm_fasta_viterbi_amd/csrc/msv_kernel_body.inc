@@ -57,7 +57,13 @@
     // 100.hmm rows are ~35 VALU, and waves spent 67% of their cycles in s_waitcnt, PMC r02).
     constexpr bool XROW2 = XROW && NPH % 2 == 0 && PF <= 2;  // +4 PF VGPRs
     static_assert(SPLIT || BIG == (LDS_ROWS < kTableRows), "BIG <=> table does not fit LDS");
-    __shared__ float4 tab[LDS_ROWS * ROW_F4];
+    // LAZY rows (hand-ordered long rows at 4 waves per SIMD: msv_kernel.h lazy_e_rows) skip the E maximum of a
+    // row on which no lane of the wave can raise its group's J (see `row`).  The per-lane bound table
+    // [21][G] floats follows the emission table in a.etab and in LDS.
+    constexpr bool LAZY = lazy_e_rows(S, WAVES, PF, BIG, SA, D);
+    constexpr int EMAX_F4 = LAZY ? kTableRows * G / 4 : 0;
+    static_assert((LDS_ROWS * ROW_F4 + EMAX_F4) * 16 <= kLdsLimit, "table and bound table fit LDS");
+    __shared__ float4 tab[LDS_ROWS * ROW_F4 + EMAX_F4];
 
     const float NINF = -__builtin_inff();
     const int lane = threadIdx.x & 63;
@@ -65,7 +71,7 @@
     const bool leader = gl == 0;
 
     // Stage the emission table (already in kernel layout) into LDS once per workgroup.
-    for (int i = threadIdx.x; i < LDS_ROWS * ROW_F4; i += WAVES * 64) tab[i] = a.etab[i];
+    for (int i = threadIdx.x; i < LDS_ROWS * ROW_F4 + EMAX_F4; i += WAVES * 64) tab[i] = a.etab[i];
     __syncthreads();
 
     const uint8_t* __restrict__ res = a.residues;
@@ -129,6 +135,7 @@
     // 4 bytes and shifts its own ones down; lanes wholly past the end (or before the buffer start, whose
     // address wrapped) hold garbage rows that are never read.
     std::conditional_t<WIDE, WideBlocks, NoWideBlocks> wb;  // WIDE only (one stream: D == 1)
+    std::conditional_t<LAZY, LazyE, NoLazyE> lz;            // LAZY only (one stream: D == 1)
     // The shift is returned separately (`sh`, bits) so a superblock requested ahead is not waited for
     // where it is requested: it is applied when the superblock becomes current.
     auto load_w = [&](uint32_t a, uint32_t e3, uint32_t& sh) __attribute__((always_inline)) -> uint32_t {
@@ -204,6 +211,10 @@
         st.B = st.move;   // dp[0][B] = tr_move (MSV_HMM.cpp:97)
         st.active = !retire;
         st.junk = !run;
+        if constexpr (LAZY) {  // J = -inf: every row is full until the group has a J
+            lz.U = NINF;
+            lz.Jg = NINF;
+        }
         if constexpr (WIDE) {
             // Block j of the stream = rows base + 16j .. base + 16j + 15, base = pos - PH; superblock m =
             // blocks 4m .. 4m + 3.  cur = block 0, nxt = block 1 (PH = 0: block 0 -- the phase-0 row first
@@ -346,7 +357,23 @@
                 "v_max_f32 %1, %2, %4"
                 : "+v"(st.M[k + 3]), "+v"(st.M[k + 2]), "+v"(st.M[k + 1])
                 : "v"(st.M[k]), "v"(rc.Bt));
-            if constexpr (!SPLIT && c == CA - 1) {  // the row's first chunk starts the E partials
+            if constexpr (LAZY) {
+                // The 8 cell ops alone, in the same max/add interleave: the lane's E maximum is taken over the
+                // whole row after its last chunk (epilogue), in one block that a lean row skips with one
+                // scalar branch.  (Skipping the two E-partial maxes chunk by chunk cost more than it saved: as
+                // a second row body behind one branch the allocator permuted M between the two paths and
+                // spilled, 400 B of scratch per lane at S = 88; as scalar branches inside this block, one or two
+                // per chunk, cfg3 ran 1.2% / 12% slower than without the skip -- profiles/r08_ab_lazy_e.md.)
+                asm volatile(
+                    "v_add_f32 %0, %6, %0\n\t"
+                    "v_max_f32 %2, %3, %5\n\t"
+                    "v_add_f32 %1, %7, %1\n\t"
+                    "v_max_f32 %3, %4, %5\n\t"
+                    "v_add_f32 %2, %8, %2\n\t"
+                    "v_add_f32 %3, %9, %3"
+                    : "+v"(st.M[k + 3]), "+v"(st.M[k + 2]), "+v"(st.M[k + 1]), "+v"(st.M[k])
+                    : "v"(mprev), "v"(rc.Bt), "v"(ev.w), "v"(ev.z), "v"(ev.y), "v"(ev.x));
+            } else if constexpr (!SPLIT && c == CA - 1) {  // the row's first chunk starts the E partials
                 asm volatile(
                     "v_add_f32 %0, %8, %0\n\t"
                     "v_max_f32 %2, %3, %7\n\t"
@@ -414,15 +441,39 @@
     };
     // Row epilogue: E over the group, the specials (MSV_HMM.cpp:107-110), cursor advance.
     auto epilogue = [&](St& st, auto& rc, auto ph) {
-        const float Elane = fmaxf(rc.p0, rc.p1);
-        // Per-lane partials (see Stream): J_l, and C_l unless C == J (tr_E_C == tr_E_J, which is
-        // always the case for the reference's nu = 2, MSV_HMM.cpp:49-53: then the C and J
-        // recurrences are identical and C is read from J at the end).
-        const float EJ = Elane + tEJ;
-        st.J = fmaxf(st.J + st.loop, EJ);
-        if (__builtin_expect(!sameEJ, 0)) {
-            st.C = fmaxf(st.C + st.loop, Elane + tEC);
-            asm volatile("" ::: "memory");  // keep a real (scalar) branch, not a per-row select
+        if constexpr (LAZY) {
+            // (`row` has already put U' into lz.U and the decayed J into lz.Jg.)  A lean row only decays J_l.
+            // A full row is the row as it was; the lane's bound then restarts from its exact maximum, and Jg,
+            // which stays the group's exact J, is re-read from the lane partials on the rows whose E beats it
+            // (a J record: wave-uniformly rare, like J >= N below).
+            float Jn = st.J + st.loop;
+            if (lz.full != 0) {
+                // the lane's maximum over the row it has just written: S / 2 three-way maxes on four chains
+                float e4[4] = {st.M[0], st.M[1], st.M[2], st.M[3]};
+#pragma unroll
+                for (int q = 4; q + 1 < S; q += 2) e4[(q / 2) & 3] = fmaxf(fmaxf(e4[(q / 2) & 3], st.M[q]), st.M[q + 1]);
+                const float Elane = fmaxf(fmaxf(e4[0], e4[1]), fmaxf(e4[2], e4[3]));
+                const float EJ = Elane + tEJ;
+                Jn = fmaxf(Jn, EJ);
+                lz.U = Elane;
+                if (__builtin_expect(__any(EJ > lz.Jg), 0)) lz.Jg = group_max<G>(Jn);
+                if (__builtin_expect(!sameEJ, 0)) {
+                    st.C = fmaxf(st.C + st.loop, Elane + tEC);
+                    asm volatile("" ::: "memory");  // (as below)
+                }
+            }
+            st.J = Jn;
+        } else {
+            const float Elane = fmaxf(rc.p0, rc.p1);
+            // Per-lane partials (see Stream): J_l, and C_l unless C == J (tr_E_C == tr_E_J, which is
+            // always the case for the reference's nu = 2, MSV_HMM.cpp:49-53: then the C and J
+            // recurrences are identical and C is read from J at the end).
+            const float EJ = Elane + tEJ;
+            st.J = fmaxf(st.J + st.loop, EJ);
+            if (__builtin_expect(!sameEJ, 0)) {
+                st.C = fmaxf(st.C + st.loop, Elane + tEC);
+                asm volatile("" ::: "memory");  // keep a real (scalar) branch, not a per-row select
+            }
         }
         st.N = st.N + st.loop;
         // B = max(N, J) + move needs the group's J = max_l J_l only if some J_l >= N; otherwise
@@ -487,9 +538,37 @@
     // slot of the residue of the row after a row of phase P
     auto next_slot = [](auto ph) { return (decltype(ph)::value + 1) % St::RPF; };
 
+    // LAZY rows.  In these kernels E has one consumer, the lane's J partial J_l = max(J_l + loop, E_l + tEJ)
+    // (C is J: the skip is off unless tr_E_C == tr_E_J), and only max_l J_l is ever read (B when J >= N, the
+    // score).  Each lane keeps U >= the maximum of its own states' previous row and Jg = the group's J.
+    // Before a row,  U' = emax[r][lane] + max3(U, left, Bt)  bounds the lane's new maximum E_l: every cell is
+    // fl(e + max(M_prev, Bt)) with e <= emax, M_prev <= U or = left (the exact M shifted in from the left
+    // lane), and fl(x + y) is monotone in both arguments.  The row is LEAN if no lane of the wave has
+    // fl(U' + tEJ) > fl(Jg + loop): then fl(E_l + tEJ) <= fl(U' + tEJ) <= fl(Jg + loop) = max_l fl(J_l + loop)
+    // for every lane, so dropping the E terms leaves max_l J_l -- hence B, the J >= N test and the score --
+    // bit for bit what the full row gives.  A lean row skips the block that takes E_l (S/2 half-rate maxes over
+    // the finished row) and the E -> J ops of the epilogue, decays J_l and Jg by loop and keeps U = U'; a full
+    // row takes E_l, then U = E_l.  Jg never exceeds the group's J: a lean row's J is fl(J + loop) exactly, and
+    // a full row re-reads Jg from the lane partials whenever some E_l + tEJ beats it (epilogue).
+    // Never lean: a poison residue (emax = +inf, so the +inf reaches the score and kErrBadResidue); the
+    // first rows of a sequence (Jg = -inf).  Retired and junk streams (Bt = -inf: U' = -inf, or NaN under
+    // a poison residue) compare as "not greater" and never force a full row.
+    const uint64_t lazy_off = sameEJ ? 0ull : ~0ull;  // wave-uniform, loop-invariant: tr_E_C != tr_E_J keeps every row full
     // All chunks of one row, C4-1 .. 0, each step pinned so only the rings' registers are live.
     auto row = [&](St& st, auto& rc, const float4* ep, auto ph) {
+        float lazy_em = 0.f;
+        if constexpr (LAZY) {
+            const uint32_t r = resid(st, ph);
+            const uint32_t rr = BLK ? r : min(r, static_cast<uint32_t>(kPoisonRow));  // (BLK residues arrive clamped)
+            lazy_em = reinterpret_cast<const float*>(tab + LDS_ROWS * ROW_F4)[rr * G + static_cast<uint32_t>(gl)];
+        }
         prologue(st, rc, ep, ph);
+        if constexpr (LAZY) {
+            lz.U = lazy_em + fmaxf(fmaxf(lz.U, rc.nbr), rc.Bt);
+            lz.Jg = lz.Jg + st.loop;
+            // (an explicit ordered compare: NaN is "not greater" whatever the floating-point flags)
+            lz.full = __builtin_amdgcn_fcmpf(lz.U + tEJ, lz.Jg, 2 /* ogt */) | lazy_off;
+        }
         if constexpr (SPLIT) {
             [&]<int... I>(std::integer_sequence<int, I...>) {
                 ((bhalf(st, rc, std::integral_constant<int, HB - 1 - I>{}),

@@ -152,6 +152,16 @@ struct WideBlocks {
 };
 struct NoWideBlocks {};
 
+// LAZY rows (lazy_e_rows variants, one stream per lane group; msv_kernel_body.inc `row`): U, an upper bound
+// on the maximum of the lane's states in the previous row; Jg, the group's J; full, the lanes that need the
+// current row's E maximum (a wave-uniform mask: the row skips it when there is none).  Kept out of Stream like
+// WideBlocks.
+struct LazyE {
+    float U, Jg;
+    uint64_t full;
+};
+struct NoLazyE {};
+
 // Per-row working set of one stream.
 template <int PF>
 struct RowCtx {

@@ -74,6 +74,26 @@ std::vector<float> msv_variant_table(const float* es, uint32_t model_length, int
     return tab;
 }
 
+// The lazy-E bound table of a whole-row variant (msv_kernel_body.inc, LAZY): [row r][lane gl] = the largest
+// emission score of residue r over the lane's states gl*S + 1 .. gl*S + S.  States beyond LENG are
+// ignored (a lane that holds only padding gets -inf); row 20, the poison row, is +inf, so a row with a
+// bad residue never passes the bound.  It follows the variant's table in the same device buffer.
+std::vector<float> msv_lazy_bound_table(const float* es, uint32_t model_length, int G, int S) {
+    const uint32_t R = model_length - 1;
+    std::vector<float> tab(static_cast<size_t>(kTableRows) * G, kPinf);
+    for (int r = 0; r < kAminoAcids; ++r)
+        for (int gl = 0; gl < G; ++gl) {
+            float m = kNinf;
+            for (int q = 0; q < S; ++q) {
+                const uint32_t j = 1 + static_cast<uint32_t>(gl * S + q);  // state 1..
+                if (j <= R && es[static_cast<size_t>(r) * model_length + j] > m)
+                    m = es[static_cast<size_t>(r) * model_length + j];
+            }
+            tab[static_cast<size_t>(r) * G + gl] = m;
+        }
+    return tab;
+}
+
 // The MSV table of a cooperative variant (msv_coop.hip) of `waves` waves, S states per lane, the first sa of
 // them staged in LDS, `halo` states shared between neighbouring waves:
 // [21 rows][waves][SA/2 chunks][64 lanes] float2 (staged in LDS): wave w, lane l, chunk h, slot q holds

@@ -261,6 +261,13 @@ msv_status msv_score_grid_device(msv_profile* const* profiles, uint32_t n_profil
  * gather) uses the same split (hmm_fasta_viterbi_amd/distributed.py). */
 msv_status msv_shard_bounds(const uint64_t* offsets, uint64_t n, uint32_t n_shards, uint64_t* bounds);
 
+/* The lazy-E bound table of a kernel variant with G lanes per sequence and S states per lane (host-only,
+ * for tests and tools): out[21 * G], out[r * G + l] = the largest of emission_scores[r][l*S + 1 .. l*S + S]
+ * (emission_scores: [20][model_length] as msv_hmm_msv_scores returns it; states past model_length - 1 are
+ * ignored, a lane with none gets -inf), row 20 = +inf.  The kernels of long whole-row variants skip a row's
+ * E maximum where this bound proves that it cannot raise J. */
+msv_status msv_lazy_bound_table(const float* emission_scores, uint32_t model_length, int G, int S, float* out);
+
 /* profiles[k]: the same model created on device k (msv_profile_create_from_hmm(k, ...)).  Shard k
  * of the batch is scored on profiles[k]'s device by its own host thread (upload, longest-first
  * order, one launch, download), all shards concurrently; scores land in input order.  The same
