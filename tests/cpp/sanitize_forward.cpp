@@ -128,6 +128,26 @@ void table_builders(std::mt19937& rng) {
             REQUIRE(msv_fwd_scan_constants(m.tsc.data(), m.M, static_cast<uint32_t>(S), dd.data(), prefix.data(),
                                            steps.data()) == MSV_OK);
             REQUIRE(prefix[0] == dd[0]);
+            if (leng == capacity) {
+                // a closed node (tests/forward_batches.py knocked()): its d->d sits in lane 32's first slot, so that
+                // lane's prefix products and every scan product over a window of lanes that holds it are exactly 0
+                Model z = m;
+                const uint32_t node = 32u * static_cast<uint32_t>(S);
+                const float ninf = -std::numeric_limits<float>::infinity();
+                for (uint32_t r = 0; r < 20; ++r) z.msc[r * z.M + node] = ninf;
+                z.tsc[node * 7 + 2] = z.tsc[node * 7 + 5] = z.tsc[node * 7 + 6] = ninf;  // m->d, d->m, d->d
+                REQUIRE(msv_fwd_scan_constants(z.tsc.data(), z.M, static_cast<uint32_t>(S), dd.data(), prefix.data(),
+                                               steps.data()) == MSV_OK);
+                for (int q = 0; q < S; ++q) REQUIRE(prefix[32 * S + q] == 0.0f);
+                for (int j = 0; j < 6; ++j)
+                    for (int l = 32; l < 64 && l < 32 + (1 << j); ++l) REQUIRE(steps[j * 64 + l] == 0.0f);
+                for (float x : steps) REQUIRE(x >= 0.0f && x <= 1.0f);
+                const std::vector<uint8_t> codes = random_codes(rng, 40);
+                double sc = 0;
+                REQUIRE(msv_fwd_cpu_score(z.msc.data(), nullptr, z.tsc.data(), z.M, z.b, z.c, z.j, codes.data(), 40,
+                                          &sc) == MSV_OK);
+                REQUIRE(std::isfinite(sc));
+            }
         }
         REQUIRE(msv_fwd_scan_constants(nullptr, 2, static_cast<uint32_t>(S), nullptr, nullptr, nullptr) ==
                 MSV_ERR_INVALID_ARGUMENT);

@@ -65,10 +65,32 @@ def cpu_scores(msc, isc, tsc, consts, codes, offsets):
     return out
 
 
-def np_forward(msc, isc, tsc, consts, codes, *, d_exits=True, inserts=True, j_loop=True, dm=True, d_reach=None):
+def _window_logsumexp(x, w):
+    """out[k] = log sum exp x[max(0, k-w+1) .. k], exactly (no difference of running sums, which would cancel
+    where the window has lost the row's dominant term): blocks of w, a prefix and a suffix scan in each, and a
+    window is the suffix of its first block joined to the prefix of its second."""
+    n = len(x)
+    nb = -(-n // w)
+    blocks = np.full(nb * w, -np.inf)
+    blocks[:n] = x
+    blocks = blocks.reshape(nb, w)
+    pre = np.logaddexp.accumulate(blocks, axis=1).ravel()
+    suf = np.logaddexp.accumulate(blocks[:, ::-1], axis=1)[:, ::-1].ravel()
+    k = np.arange(n)
+    lo = np.maximum(k - w + 1, 0)
+    whole = (lo % w == 0) & (k - lo == w - 1)  # the window is one block: its suffix alone
+    return np.where(whole | (k < w), pre[k], np.logaddexp(suf[lo], pre[k]))
+
+
+def np_forward(msc, isc, tsc, consts, codes, *, d_exits=True, inserts=True, j_loop=True, dm=True, d_reach=None,
+               d_scan=False):
     """The model of msv.h in LOG space, float64, vectorised over k with np.logaddexp; the in-row D chain is a
-    plain loop.  Switches remove one term each: the D -> E exits, the I states, the J loop, the d->m transitions;
-    d_reach = r cuts every D chain after r d->d steps (D mass from more than r states upstream is dropped)."""
+    plain loop over the states (over the steps for a cut), or with d_scan one accumulate.  Switches remove one
+    term each: the D -> E exits, the I states, the J loop, the d->m transitions;
+    d_reach = r cuts every D chain after r d->d steps (D mass from more than r states upstream is dropped).
+    d_scan = True restates the D chain for long models whose d->d are all finite: with P[j] the sum of d->d over
+    nodes 1 .. j, D(k) = P[k-1] + log sum over sources s of exp(M(s) + m->d(s) - P[s]), s = k-1-r .. k-1 -- one
+    np.logaddexp.accumulate (a windowed one for the cut) instead of a loop over states or over steps."""
     tBM, tEC, tEJ = (float(x) for x in consts)
     M = msc.shape[1]
     K = M - 1
@@ -95,7 +117,14 @@ def np_forward(msc, isc, tsc, consts, codes, *, d_exits=True, inserts=True, j_lo
             Mc[1:] = m[r, 1:] + la(prev, B + tBM)
             if inserts:
                 Ic[1:K] = ins[r, 1:K] + la(Mp[1:K] + t[1:K, MI], Ip[1:K] + t[1:K, II])
-        if d_reach is None:
+        if d_scan:
+            P = np.zeros(M)
+            P[1:K] = np.cumsum(t[1:K, DD])
+            P[K:] = P[K - 1] if K > 1 else 0.0
+            x = Mc + t[:, MD] - P  # (node 0 and node LENG have no m->d: -inf)
+            acc = np.logaddexp.accumulate(x) if d_reach is None else _window_logsumexp(x, d_reach + 1)
+            Dc[2:] = acc[1:-1] + P[1:-1]
+        elif d_reach is None:
             for k in range(2, M):
                 Dc[k] = la(Mc[k - 1] + t[k - 1, MD], Dc[k - 1] + t[k - 1, DD])
         else:  # D(k) = sum over sources s = k-1, k-2, .. k-1-d_reach of M(s) tMD(s) prod tDD

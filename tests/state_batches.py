@@ -40,11 +40,8 @@ def _csr(seqs) -> tuple[np.ndarray, np.ndarray]:
     return codes, offsets
 
 
-def tail_homolog_batch(match_emissions: np.ndarray, seed: int, n: int, lmin: int, lmax: int,
-                       mutate: float = 0.1) -> tuple[np.ndarray, np.ndarray]:
-    """synthetic.homolog_batch with the core's end pinned to the LAST state: a sequence of length U[lmin, lmax]
-    (lmin >= 1) whose core of U[L/2, L] residues (at most LENG) is emitted by the states LENG - core + 1 .. LENG,
-    wrapped in uniform flanks."""
+def _end_homolog_batch(match_emissions: np.ndarray, seed: int, n: int, lmin: int, lmax: int, mutate: float,
+                       head: bool) -> tuple[np.ndarray, np.ndarray]:
     rng = np.random.Generator(np.random.PCG64(seed))
     cdf = _cdf(match_emissions)
     leng = cdf.shape[0]
@@ -52,12 +49,26 @@ def tail_homolog_batch(match_emissions: np.ndarray, seed: int, n: int, lmin: int
     for _ in range(n):
         L = int(rng.integers(lmin, lmax + 1))
         core = min(L, leng, int(rng.integers(max(1, L // 2), L + 1)))
-        emitted = _emit(rng, cdf, leng - core, core, mutate)
+        emitted = _emit(rng, cdf, 0 if head else leng - core, core, mutate)
         left = int(rng.integers(0, L - core + 1))
         seq = rng.integers(0, 20, size=L, dtype=np.uint8)
         seq[left:left + core] = emitted
         seqs.append(seq)
     return _csr(seqs)
+
+
+def tail_homolog_batch(match_emissions: np.ndarray, seed: int, n: int, lmin: int, lmax: int,
+                       mutate: float = 0.1) -> tuple[np.ndarray, np.ndarray]:
+    """synthetic.homolog_batch with the core's end pinned to the LAST state: a sequence of length U[lmin, lmax]
+    (lmin >= 1) whose core of U[L/2, L] residues (at most LENG) is emitted by the states LENG - core + 1 .. LENG,
+    wrapped in uniform flanks."""
+    return _end_homolog_batch(match_emissions, seed, n, lmin, lmax, mutate, head=False)
+
+
+def head_homolog_batch(match_emissions: np.ndarray, seed: int, n: int, lmin: int, lmax: int,
+                       mutate: float = 0.1) -> tuple[np.ndarray, np.ndarray]:
+    """tail_homolog_batch mirrored: the core's START pinned to state 1 (emitted by the states 1 .. core)."""
+    return _end_homolog_batch(match_emissions, seed, n, lmin, lmax, mutate, head=True)
 
 
 def window_homolog_batch(match_emissions: np.ndarray, seed: int, starts, core: int, mutate: float = 0.1,
