@@ -108,6 +108,40 @@ def pack_sequences(seqs: Sequence[str]) -> tuple[np.ndarray, np.ndarray]:
     return encode(body), offsets
 
 
+def _batch(seqs, codes, offsets) -> tuple[np.ndarray, np.ndarray, int]:
+    """A host batch as the C-ABI takes it: (codes uint8, offsets uint64[n+1], n), both contiguous; `seqs`
+    ('#'-prefixed strings), when given, are packed into them."""
+    if seqs is not None:
+        codes, offsets = pack_sequences(seqs)
+    codes = np.ascontiguousarray(codes, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    return codes, offsets, len(offsets) - 1
+
+
+def _ptr(a: np.ndarray):
+    """The array's address, NULL for an empty one."""
+    return a.ctypes.data if a.size else None
+
+
+def _check_residues(status: int, what: str = "") -> None:
+    """check(), with a residue outside the 20 as the reference's IndexError (amino_acid_num.at, MSV_HMM.cpp:101)."""
+    if status == _native.MSV_ERR_BAD_RESIDUE:
+        raise IndexError("residue outside the 20 amino acids")
+    check(status, what)
+
+
+def _pvalues(fn: str, scores: np.ndarray, offsets: np.ndarray, location: float, scale: float) -> np.ndarray:
+    """Host P-values (msv_pvalues / msv_fwd_pvalues) of n scores, lengths from the offsets -> float64 [n]."""
+    scores = np.ascontiguousarray(scores, np.float32)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    n = len(offsets) - 1
+    if scores.shape != (n,):
+        raise ValueError("scores and offsets disagree")
+    out = np.zeros(n, np.float64)
+    check(getattr(_native.lib(), fn)(scores.ctypes.data, offsets.ctypes.data, n, location, scale, out.ctypes.data), fn)
+    return out
+
+
 class Profile_HMM:
     """Parsed HMMER3 profile (C++ parser in libmsv_hip.so, Profile_HMM.cpp:48-60 semantics)."""
 
@@ -212,37 +246,27 @@ class MSV_HMM:
         """Scores of a host batch (msv_score_batch).  Page-locked `codes` (msv.pinned_empty, torch
         pin_memory().numpy()) are read by the kernel in place, with no staging copy; a page-locked `out`
         (float32[n]) is written by the kernel directly."""
-        if seqs is not None:
-            codes, offsets = pack_sequences(seqs)
-        codes = np.ascontiguousarray(codes, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
+        codes, offsets, n = _batch(seqs, codes, offsets)
         if out is None:
             out = np.zeros(n, np.float32)
         elif out.dtype != np.float32 or out.shape != (n,) or not out.flags.c_contiguous:
             raise ValueError("out must be a contiguous float32 array of n scores")
-        st = _native.lib().msv_score_batch(self._p, codes.ctypes.data if codes.size else None, offsets.ctypes.data,
-                                           n, out.ctypes.data, None)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_score_batch")
+        _check_residues(_native.lib().msv_score_batch(self._p, _ptr(codes), offsets.ctypes.data, n, out.ctypes.data,
+                                                      None), "msv_score_batch")
         return out
 
     def score_batch_async(self, codes: np.ndarray, offsets: np.ndarray, out: np.ndarray | None = None) -> int:
         """Enqueue a host batch (msv_score_batch_async) and return a ticket; `wait(ticket)` returns
         the scores.  At most three calls outstanding; pinned arrays (torch pin_memory().numpy()) make
         the copies overlap the previous call's kernel.  The arrays are held until the wait."""
-        codes = np.ascontiguousarray(codes, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
+        codes, offsets, n = _batch(None, codes, offsets)
         if out is None:
             out = np.zeros(n, np.float32)
         if out.dtype != np.float32 or out.shape != (n,) or not out.flags.c_contiguous:
             raise ValueError("out must be a contiguous float32 array of n scores")
         t = C.c_uint64(0)
-        check(_native.lib().msv_score_batch_async(self._p, codes.ctypes.data if codes.size else None,
-                                                  offsets.ctypes.data, n, out.ctypes.data, C.byref(t)),
-              "msv_score_batch_async")
+        check(_native.lib().msv_score_batch_async(self._p, _ptr(codes), offsets.ctypes.data, n, out.ctypes.data,
+                                                  C.byref(t)), "msv_score_batch_async")
         self._inflight[t.value] = (codes, offsets, out)
         return t.value
 
@@ -250,9 +274,7 @@ class MSV_HMM:
         """Scores of an msv_score_batch_async call (raises its kernel-latched errors)."""
         st = _native.lib().msv_profile_wait(self._p, ticket)
         _, _, out = self._inflight.pop(ticket, (None, None, None))
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_profile_wait")
+        _check_residues(st, "msv_profile_wait")
         return out
 
     def score_batch_device(self, residues_ptr: int, residues_len: int, offsets_ptr: int, n: int, scores_ptr: int,
@@ -271,10 +293,7 @@ class MSV_HMM:
         check(_native.lib().msv_profile_bind_stream(self._p, stream), "msv_profile_bind_stream")
 
     def check(self, stream: int | None = None) -> None:
-        st = _native.lib().msv_profile_check(self._p, stream)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_profile_check")
+        _check_residues(_native.lib().msv_profile_check(self._p, stream), "msv_profile_check")
 
     def reserve_length(self, max_length: int) -> None:
         check(_native.lib().msv_profile_reserve_length(self._p, max_length))
@@ -282,15 +301,7 @@ class MSV_HMM:
     # -- MSV filter stage (HMMER3 formula, parity unpinned) --------------------
     def pvalues(self, scores: np.ndarray, offsets: np.ndarray) -> np.ndarray:
         """P-values of MSV scores against this profile's STATS LOCAL MSV Gumbel (msv.h)."""
-        scores = np.ascontiguousarray(scores, np.float32)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
-        if scores.shape != (n,):
-            raise ValueError("scores and offsets disagree")
-        out = np.zeros(n, np.float64)
-        check(_native.lib().msv_pvalues(scores.ctypes.data, offsets.ctypes.data, n, self.msv_mu, self.msv_lambda,
-                                        out.ctypes.data), "msv_pvalues")
-        return out
+        return _pvalues("msv_pvalues", scores, offsets, self.msv_mu, self.msv_lambda)
 
     def pvalues_device(self, scores_ptr: int, offsets_ptr: int, n: int, pvalues_ptr: int,
                        stream: int | None = None) -> None:
@@ -311,10 +322,8 @@ class MSV_HMM:
     def score_fasta_device(self, fasta: "FASTA_device") -> np.ndarray:
         """Scores of a GPU-parsed FASTA set (msv_score_fasta_device): no host parse, no H2D of residues."""
         out = np.zeros(fasta.count, np.float32)
-        st = _native.lib().msv_score_fasta_device(self._p, fasta._f, out.ctypes.data)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_score_fasta_device")
+        _check_residues(_native.lib().msv_score_fasta_device(self._p, fasta._f, out.ctypes.data),
+                        "msv_score_fasta_device")
         return out
 
     def set_variant(self, name: str) -> None:
@@ -426,15 +435,18 @@ def _cpu_trace(msc, isc, tsc, consts, codes):
     return st, np.float32(sc.value), doms, ops
 
 
-class Viterbi_HMM:
-    """Viterbi stage for one profile on one GPU (SURVEY 8(f)-4): HMMER3's generic local Viterbi over the
-    reference's parse (insert emissions, 7 transitions per node: Profile_HMM.cpp:107-120) with the MSV
-    path's specials (MSV_HMM.cpp:49-64); msv.h states the recurrence.  Every score comes from the gfx950
-    kernel (vit_kernel.hip) except run_on_sequence, which -- like the reference's MSV run_on_sequence --
-    is the library's serial CPU DP.  P-values use STATS LOCAL VITERBI (Profile_HMM.cpp:86-87)."""
+class _StageEngine:
+    """What Viterbi_HMM and Forward_HMM share: one stage profile (msv_vit_* / msv_fwd_*, the same entry points
+    under two prefixes) over the log-odds tables of msv_hmm_viterbi_scores, on one GPU."""
+
+    _prefix = ""  # the C symbols' prefix
+    _Info = None  # the describe struct
+
+    @classmethod
+    def _fn(cls, name: str):
+        return getattr(_native.lib(), f"{cls._prefix}_{name}")
 
     def __init__(self, base_hmm: Profile_HMM, device: int = 0, insert_mode: int = INSERTS_ZERO):
-        L = _native.lib()
         M = base_hmm.model_length
         self.model_length = M
         self.insert_mode = insert_mode
@@ -442,17 +454,84 @@ class Viterbi_HMM:
         self.insert_scores = np.zeros((20, M), np.float32)
         self.transition_scores = np.zeros((M, 7), np.float32)
         b, c, j = C.c_float(), C.c_float(), C.c_float()
-        check(L.msv_hmm_viterbi_scores(base_hmm._h, insert_mode, self.match_scores.ctypes.data,
-                                       self.insert_scores.ctypes.data, self.transition_scores.ctypes.data,
-                                       C.byref(b), C.byref(c), C.byref(j)), "msv_hmm_viterbi_scores")
+        check(_native.lib().msv_hmm_viterbi_scores(
+            base_hmm._h, insert_mode, self.match_scores.ctypes.data, self.insert_scores.ctypes.data,
+            self.transition_scores.ctypes.data, C.byref(b), C.byref(c), C.byref(j)), "msv_hmm_viterbi_scores")
         self.tr_B_Mk, self.tr_E_C, self.tr_E_J = b.value, c.value, j.value
         p = C.c_void_p()
-        check(L.msv_vit_profile_create(device, self.match_scores.ctypes.data,
-                                       self.insert_scores.ctypes.data if insert_mode == INSERTS_LOG_ODDS else None,
-                                       self.transition_scores.ctypes.data, M, self.tr_B_Mk, self.tr_E_C, self.tr_E_J,
-                                       C.byref(p)), "msv_vit_profile_create")
+        check(self._fn("profile_create")(device, *self._tables(), C.byref(p)), f"{self._prefix}_profile_create")
         self._p = p
         self.device = device
+
+    def _tables(self):
+        """The model as the create and CPU entry points take it (insert scores NULL for HMMER3's zeros)."""
+        return (self.match_scores.ctypes.data, self.insert_scores.ctypes.data if self.insert_mode else None,
+                self.transition_scores.ctypes.data, self.model_length, self.tr_B_Mk, self.tr_E_C, self.tr_E_J)
+
+    def parallel_run_on_sequence(self, seq: str) -> float:
+        return float(self.score_batch([seq])[0])
+
+    def score_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
+                    offsets: np.ndarray | None = None) -> np.ndarray:
+        """This stage's scores of every sequence of a host batch (msv_*_score_batch, one launch)."""
+        codes, offsets, n = _batch(seqs, codes, offsets)
+        out = np.zeros(n, np.float32)
+        _check_residues(self._fn("score_batch")(self._p, _ptr(codes), offsets.ctypes.data, n, out.ctypes.data, None),
+                        f"{self._prefix}_score_batch")
+        return out
+
+    def score_batch_device(self, residues_ptr: int, residues_len: int, offsets_ptr: int, n: int, scores_ptr: int,
+                           select_ptr: int | None = None, select_count_ptr: int | None = None,
+                           stream: int | None = None) -> None:
+        """Device-resident batch (raw device pointers), optionally only the sequences listed at select_ptr
+        (uint32; their count in the device uint32 at select_count_ptr, else n); async on `stream`."""
+        check(self._fn("score_batch_device")(self._p, residues_ptr, residues_len, offsets_ptr, n, select_ptr,
+                                             select_count_ptr, scores_ptr, stream),
+              f"{self._prefix}_score_batch_device")
+
+    def reserve_length(self, max_length: int) -> None:
+        check(self._fn("profile_reserve_length")(self._p, max_length))
+
+    def bind_stream(self, stream: int | None) -> None:
+        """msv_*_profile_bind_stream: launches on this (caller-kept-alive) stream skip the slot event."""
+        check(self._fn("profile_bind_stream")(self._p, stream), f"{self._prefix}_profile_bind_stream")
+
+    def check(self, stream: int | None = None) -> None:
+        _check_residues(self._fn("profile_check")(self._p, stream), f"{self._prefix}_profile_check")
+
+    def set_variant(self, name: str) -> None:
+        check(self._fn("profile_set_variant")(self._p, name.encode()), f"set_variant({name})")
+
+    @classmethod
+    def variants(cls) -> list[str]:
+        return [cls._fn("variant_name")(i).decode() for i in range(cls._fn("variant_count")())]
+
+    def describe(self) -> dict:
+        info = self._Info()
+        check(self._fn("profile_describe")(self._p, C.byref(info)))
+        return info.as_dict()
+
+    def close(self):
+        lib = _loaded_lib()
+        if getattr(self, "_p", None) and lib is not None:
+            getattr(lib, f"{self._prefix}_profile_destroy")(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
+
+
+class Viterbi_HMM(_StageEngine):
+    """Viterbi stage for one profile on one GPU (SURVEY 8(f)-4): HMMER3's generic local Viterbi over the
+    reference's parse (insert emissions, 7 transitions per node: Profile_HMM.cpp:107-120) with the MSV
+    path's specials (MSV_HMM.cpp:49-64); msv.h states the recurrence.  Every score comes from the gfx950
+    kernel (vit_kernel.hip) except run_on_sequence, which -- like the reference's MSV run_on_sequence --
+    is the library's serial CPU DP.  P-values use STATS LOCAL VITERBI (Profile_HMM.cpp:86-87)."""
+
+    _prefix, _Info = "msv_vit", _native.VitInfo
+
+    def __init__(self, base_hmm: Profile_HMM, device: int = 0, insert_mode: int = INSERTS_ZERO):
+        super().__init__(base_hmm, device, insert_mode)
         self.viterbi_mu = base_hmm.stats_local_viterbi_mu
         self.viterbi_lambda = base_hmm.stats_local_viterbi_lambda
 
@@ -460,31 +539,9 @@ class Viterbi_HMM:
         """The serial CPU Viterbi (msv_vit_cpu_score); IndexError on a residue outside the 20."""
         codes = encode(seq[1:] if seq.startswith("#") else seq)
         out = C.c_float()
-        st = _native.lib().msv_vit_cpu_score(
-            self.match_scores.ctypes.data, self.insert_scores.ctypes.data if self.insert_mode else None,
-            self.transition_scores.ctypes.data, self.model_length, self.tr_B_Mk, self.tr_E_C, self.tr_E_J,
-            codes.ctypes.data if codes.size else None, codes.size, C.byref(out))
-        check(st, "msv_vit_cpu_score")
+        check(_native.lib().msv_vit_cpu_score(*self._tables(), _ptr(codes), codes.size, C.byref(out)),
+              "msv_vit_cpu_score")
         return out.value
-
-    def parallel_run_on_sequence(self, seq: str) -> float:
-        return float(self.score_batch([seq])[0])
-
-    def score_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
-                    offsets: np.ndarray | None = None) -> np.ndarray:
-        """Viterbi scores of every sequence of a host batch (msv_vit_score_batch, one launch)."""
-        if seqs is not None:
-            codes, offsets = pack_sequences(seqs)
-        codes = np.ascontiguousarray(codes, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
-        out = np.zeros(n, np.float32)
-        st = _native.lib().msv_vit_score_batch(self._p, codes.ctypes.data if codes.size else None,
-                                               offsets.ctypes.data, n, out.ctypes.data, None)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_vit_score_batch")
-        return out
 
     def _consensus(self):
         return self.match_scores.argmax(axis=0), self.match_scores > 0
@@ -497,25 +554,19 @@ class Viterbi_HMM:
         for back-pointers (0: the default of trace_describe()); the call runs in as many chunks as that takes.
         A bad residue raises IndexError as score_batch does, unless strict=False: then the traces are returned
         with `status` set, the bad entries without domains."""
-        if seqs is not None:
-            codes, offsets = pack_sequences(seqs)
-        codes = np.ascontiguousarray(codes, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
+        codes, offsets, n = _batch(seqs, codes, offsets)
         sel = None if select is None else np.ascontiguousarray(select, np.uint32)
         sel_buf = sel if sel is None or sel.size else np.zeros(1, np.uint32)  # (an empty list is not "every one")
         L = _native.lib()
         t = C.c_void_p()
-        st = L.msv_vit_trace_batch(self._p, codes.ctypes.data if codes.size else None, offsets.ctypes.data, n,
+        st = L.msv_vit_trace_batch(self._p, _ptr(codes), offsets.ctypes.data, n,
                                    None if sel is None else sel_buf.ctypes.data,
                                    0 if sel is None else sel.size, workspace_bytes, C.byref(t))
         if not t.value:
             check(st, "msv_vit_trace_batch")
         try:
-            if st != _native.MSV_OK and strict:
-                if st == _native.MSV_ERR_BAD_RESIDUE:
-                    raise IndexError("residue outside the 20 amino acids")
-                check(st, "msv_vit_trace_batch")
+            if strict:
+                _check_residues(st, "msv_vit_trace_batch")
             m = L.msv_vit_traces_count(t)
             scores = np.zeros(m, np.float32)
             dom_off = np.zeros(m + 1, np.uint64)
@@ -538,9 +589,7 @@ class Viterbi_HMM:
         codes = np.ascontiguousarray(codes, np.uint8)
         st, sc, doms, ops = _cpu_trace(self.match_scores, self.insert_scores if self.insert_mode else None,
                                        self.transition_scores, (self.tr_B_Mk, self.tr_E_C, self.tr_E_J), codes)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_vit_cpu_trace")
+        _check_residues(st, "msv_vit_cpu_trace")
         return Traces(np.array([sc], np.float32), np.array([0, len(doms)], np.uint64), doms, ops, codes=codes,
                       offsets=np.array([0, codes.size], np.uint64), consensus=self._consensus())
 
@@ -556,61 +605,9 @@ class Viterbi_HMM:
         check(_native.lib().msv_vit_trace_describe(self._p, C.byref(info)), "msv_vit_trace_describe")
         return info.as_dict()
 
-    def score_batch_device(self, residues_ptr: int, residues_len: int, offsets_ptr: int, n: int, scores_ptr: int,
-                           select_ptr: int | None = None, select_count_ptr: int | None = None,
-                           stream: int | None = None) -> None:
-        """Device-resident batch (raw device pointers), optionally only the sequences listed at select_ptr
-        (uint32; their count in the device uint32 at select_count_ptr, else n); async on `stream`."""
-        check(_native.lib().msv_vit_score_batch_device(self._p, residues_ptr, residues_len, offsets_ptr, n,
-                                                       select_ptr, select_count_ptr, scores_ptr, stream),
-              "msv_vit_score_batch_device")
-
-    def reserve_length(self, max_length: int) -> None:
-        check(_native.lib().msv_vit_profile_reserve_length(self._p, max_length))
-
-    def bind_stream(self, stream: int | None) -> None:
-        """msv_vit_profile_bind_stream: launches on this (caller-kept-alive) stream skip the slot event."""
-        check(_native.lib().msv_vit_profile_bind_stream(self._p, stream), "msv_vit_profile_bind_stream")
-
-    def check(self, stream: int | None = None) -> None:
-        st = _native.lib().msv_vit_profile_check(self._p, stream)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_vit_profile_check")
-
     def pvalues(self, scores: np.ndarray, offsets: np.ndarray) -> np.ndarray:
         """P-values of Viterbi scores against STATS LOCAL VITERBI (HMMER3's formula, msv_pvalues)."""
-        scores = np.ascontiguousarray(scores, np.float32)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
-        if scores.shape != (n,):
-            raise ValueError("scores and offsets disagree")
-        out = np.zeros(n, np.float64)
-        check(_native.lib().msv_pvalues(scores.ctypes.data, offsets.ctypes.data, n, self.viterbi_mu,
-                                        self.viterbi_lambda, out.ctypes.data), "msv_pvalues")
-        return out
-
-    def set_variant(self, name: str) -> None:
-        check(_native.lib().msv_vit_profile_set_variant(self._p, name.encode()), f"set_variant({name})")
-
-    @staticmethod
-    def variants() -> list[str]:
-        L = _native.lib()
-        return [L.msv_vit_variant_name(i).decode() for i in range(L.msv_vit_variant_count())]
-
-    def describe(self) -> dict:
-        info = _native.VitInfo()
-        check(_native.lib().msv_vit_profile_describe(self._p, C.byref(info)))
-        return info.as_dict()
-
-    def close(self):
-        lib = _loaded_lib()
-        if getattr(self, "_p", None) and lib is not None:
-            lib.msv_vit_profile_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
+        return _pvalues("msv_pvalues", scores, offsets, self.viterbi_mu, self.viterbi_lambda)
 
 
 def filter_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, seqs: Sequence[str] | None = None, *,
@@ -621,21 +618,14 @@ def filter_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, seqs: Sequence
     (STATS LOCAL VITERBI, NaN elsewhere).  Returns (msv_scores, passed, vit_scores, vit_pvalues); with
     align=True also the Traces of the sequences that passed, in index order (a second call that uploads the
     batch again: Viterbi_HMM.trace_batch with select = the passed indices)."""
-    if seqs is not None:
-        codes, offsets = pack_sequences(seqs)
-    codes = np.ascontiguousarray(codes, np.uint8)
-    offsets = np.ascontiguousarray(offsets, np.uint64)
-    n = len(offsets) - 1
+    codes, offsets, n = _batch(seqs, codes, offsets)
     msc = np.zeros(n, np.float32)
     passed = np.zeros(n, np.uint8)
     vsc = np.zeros(n, np.float32)
     npass = C.c_uint64(0)
-    st = _native.lib().msv_vit_filter_batch(msv_engine._p, vit_engine._p, codes.ctypes.data if codes.size else None,
-                                            offsets.ctypes.data, n, msv_engine.msv_mu, msv_engine.msv_lambda, F1,
-                                            msc.ctypes.data, passed.ctypes.data, vsc.ctypes.data, C.byref(npass))
-    if st == _native.MSV_ERR_BAD_RESIDUE:
-        raise IndexError("residue outside the 20 amino acids")
-    check(st, "msv_vit_filter_batch")
+    _check_residues(_native.lib().msv_vit_filter_batch(
+        msv_engine._p, vit_engine._p, _ptr(codes), offsets.ctypes.data, n, msv_engine.msv_mu, msv_engine.msv_lambda,
+        F1, msc.ctypes.data, passed.ctypes.data, vsc.ctypes.data, C.byref(npass)), "msv_vit_filter_batch")
     mask = passed.astype(bool)
     vpv = np.full(n, np.nan)
     if mask.any():
@@ -646,143 +636,46 @@ def filter_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, seqs: Sequence
     return msc, mask, vsc, vpv
 
 
-class Forward_HMM:
+class Forward_HMM(_StageEngine):
     """Forward stage for one profile on one GPU (msv.h "Forward stage"): the log, in nats, of the summed
     odds of EVERY alignment -- the score HMMER3's E-values come from.  Same tables and specials as Viterbi_HMM, plus
     the D_k -> E exits.  Every score comes from the gfx950 kernel (fwd_kernel.hip, float32 odds with exact
     power-of-two rescaling) except run_on_sequence, the library's serial float64 CPU Forward, which every test
     compares against.  P-values use STATS LOCAL FORWARD."""
 
+    _prefix, _Info = "msv_fwd", _native.FwdInfo
+
     def __init__(self, base_hmm: Profile_HMM, device: int = 0, insert_mode: int = INSERTS_ZERO):
-        L = _native.lib()
-        M = base_hmm.model_length
-        self.model_length = M
-        self.insert_mode = insert_mode
-        self.match_scores = np.zeros((20, M), np.float32)
-        self.insert_scores = np.zeros((20, M), np.float32)
-        self.transition_scores = np.zeros((M, 7), np.float32)
-        b, c, j = C.c_float(), C.c_float(), C.c_float()
-        check(L.msv_hmm_viterbi_scores(base_hmm._h, insert_mode, self.match_scores.ctypes.data,
-                                       self.insert_scores.ctypes.data, self.transition_scores.ctypes.data,
-                                       C.byref(b), C.byref(c), C.byref(j)), "msv_hmm_viterbi_scores")
-        self.tr_B_Mk, self.tr_E_C, self.tr_E_J = b.value, c.value, j.value
-        p = C.c_void_p()
-        check(L.msv_fwd_profile_create(device, self.match_scores.ctypes.data,
-                                       self.insert_scores.ctypes.data if insert_mode == INSERTS_LOG_ODDS else None,
-                                       self.transition_scores.ctypes.data, M, self.tr_B_Mk, self.tr_E_C, self.tr_E_J,
-                                       C.byref(p)), "msv_fwd_profile_create")
-        self._p = p
-        self.device = device
+        super().__init__(base_hmm, device, insert_mode)
         self.forward_tau = base_hmm.stats_local_forward_theta
         self.forward_lambda = base_hmm.stats_local_forward_lambda
-
-    def _tables(self):
-        return (self.match_scores.ctypes.data, self.insert_scores.ctypes.data if self.insert_mode else None,
-                self.transition_scores.ctypes.data, self.model_length, self.tr_B_Mk, self.tr_E_C, self.tr_E_J)
 
     def run_on_sequence(self, seq: str) -> float:
         """The serial float64 CPU Forward (msv_fwd_cpu_score); IndexError on a residue outside the 20."""
         codes = encode(seq[1:] if seq.startswith("#") else seq)
         out = C.c_double()
-        check(_native.lib().msv_fwd_cpu_score(*self._tables(), codes.ctypes.data if codes.size else None,
-                                              codes.size, C.byref(out)), "msv_fwd_cpu_score")
+        check(_native.lib().msv_fwd_cpu_score(*self._tables(), _ptr(codes), codes.size, C.byref(out)),
+              "msv_fwd_cpu_score")
         return out.value
 
     def cpu_score_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
                         offsets: np.ndarray | None = None) -> np.ndarray:
         """run_on_sequence over a host batch (msv_fwd_cpu_score_batch, a few host threads) -> float64 [n]."""
-        if seqs is not None:
-            codes, offsets = pack_sequences(seqs)
-        codes = np.ascontiguousarray(codes, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
+        codes, offsets, n = _batch(seqs, codes, offsets)
         out = np.zeros(n, np.float64)
-        st = _native.lib().msv_fwd_cpu_score_batch(*self._tables(), codes.ctypes.data if codes.size else None,
-                                                   offsets.ctypes.data, n, out.ctypes.data)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_fwd_cpu_score_batch")
+        _check_residues(_native.lib().msv_fwd_cpu_score_batch(*self._tables(), _ptr(codes), offsets.ctypes.data, n,
+                                                              out.ctypes.data), "msv_fwd_cpu_score_batch")
         return out
-
-    def parallel_run_on_sequence(self, seq: str) -> float:
-        return float(self.score_batch([seq])[0])
-
-    def score_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
-                    offsets: np.ndarray | None = None) -> np.ndarray:
-        """Forward scores of every sequence of a host batch (msv_fwd_score_batch, one launch)."""
-        if seqs is not None:
-            codes, offsets = pack_sequences(seqs)
-        codes = np.ascontiguousarray(codes, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
-        out = np.zeros(n, np.float32)
-        st = _native.lib().msv_fwd_score_batch(self._p, codes.ctypes.data if codes.size else None,
-                                               offsets.ctypes.data, n, out.ctypes.data, None)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_fwd_score_batch")
-        return out
-
-    def score_batch_device(self, residues_ptr: int, residues_len: int, offsets_ptr: int, n: int, scores_ptr: int,
-                           select_ptr: int | None = None, select_count_ptr: int | None = None,
-                           stream: int | None = None) -> None:
-        """Device-resident batch (raw device pointers), optionally only the sequences listed at select_ptr
-        (uint32; their count in the device uint32 at select_count_ptr, else n); async on `stream`."""
-        check(_native.lib().msv_fwd_score_batch_device(self._p, residues_ptr, residues_len, offsets_ptr, n,
-                                                       select_ptr, select_count_ptr, scores_ptr, stream),
-              "msv_fwd_score_batch_device")
-
-    def reserve_length(self, max_length: int) -> None:
-        check(_native.lib().msv_fwd_profile_reserve_length(self._p, max_length))
-
-    def bind_stream(self, stream: int | None) -> None:
-        check(_native.lib().msv_fwd_profile_bind_stream(self._p, stream), "msv_fwd_profile_bind_stream")
-
-    def check(self, stream: int | None = None) -> None:
-        st = _native.lib().msv_fwd_profile_check(self._p, stream)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_fwd_profile_check")
 
     def pvalues(self, scores: np.ndarray, offsets: np.ndarray) -> np.ndarray:
         """P-values of Forward scores against STATS LOCAL FORWARD (msv_fwd_pvalues)."""
-        scores = np.ascontiguousarray(scores, np.float32)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
-        if scores.shape != (n,):
-            raise ValueError("scores and offsets disagree")
-        out = np.zeros(n, np.float64)
-        check(_native.lib().msv_fwd_pvalues(scores.ctypes.data, offsets.ctypes.data, n, self.forward_tau,
-                                            self.forward_lambda, out.ctypes.data), "msv_fwd_pvalues")
-        return out
+        return _pvalues("msv_fwd_pvalues", scores, offsets, self.forward_tau, self.forward_lambda)
 
     def pvalues_device(self, scores_ptr: int, offsets_ptr: int, n: int, pvalues_ptr: int,
                        stream: int | None = None) -> None:
         """Device P-values (float64 out) for device scores/offsets, async on `stream`."""
         check(_native.lib().msv_fwd_pvalues_device(self.device, scores_ptr, offsets_ptr, n, self.forward_tau,
                                                    self.forward_lambda, pvalues_ptr, stream), "msv_fwd_pvalues_device")
-
-    def set_variant(self, name: str) -> None:
-        check(_native.lib().msv_fwd_profile_set_variant(self._p, name.encode()), f"set_variant({name})")
-
-    @staticmethod
-    def variants() -> list[str]:
-        L = _native.lib()
-        return [L.msv_fwd_variant_name(i).decode() for i in range(L.msv_fwd_variant_count())]
-
-    def describe(self) -> dict:
-        info = _native.FwdInfo()
-        check(_native.lib().msv_fwd_profile_describe(self._p, C.byref(info)))
-        return info.as_dict()
-
-    def close(self):
-        lib = _loaded_lib()
-        if getattr(self, "_p", None) and lib is not None:
-            lib.msv_fwd_profile_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
 
 
 def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Forward_HMM,
@@ -791,25 +684,17 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
     """HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV over every sequence, P <= F1, Viterbi on the
     survivors, P <= F2, Forward on those, Forward P-values.  Returns the per-stage arrays: msv_scores, passed_msv,
     vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run)."""
-    if seqs is not None:
-        codes, offsets = pack_sequences(seqs)
-    codes = np.ascontiguousarray(codes, np.uint8)
-    offsets = np.ascontiguousarray(offsets, np.uint64)
-    n = len(offsets) - 1
+    codes, offsets, n = _batch(seqs, codes, offsets)
     stats = np.array([msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
                       fwd_engine.forward_tau, fwd_engine.forward_lambda], np.float32)
     msc, vsc, fsc = (np.zeros(n, np.float32) for _ in range(3))
     p1, p2 = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
     fpv = np.zeros(n, np.float64)
     n1, n2 = C.c_uint64(0), C.c_uint64(0)
-    st = _native.lib().msv_fwd_filter_batch(msv_engine._p, vit_engine._p, fwd_engine._p,
-                                            codes.ctypes.data if codes.size else None, offsets.ctypes.data, n,
-                                            stats.ctypes.data, F1, F2, msc.ctypes.data, p1.ctypes.data,
-                                            vsc.ctypes.data, p2.ctypes.data, fsc.ctypes.data, fpv.ctypes.data,
-                                            C.byref(n1), C.byref(n2))
-    if st == _native.MSV_ERR_BAD_RESIDUE:
-        raise IndexError("residue outside the 20 amino acids")
-    check(st, "msv_fwd_filter_batch")
+    _check_residues(_native.lib().msv_fwd_filter_batch(
+        msv_engine._p, vit_engine._p, fwd_engine._p, _ptr(codes), offsets.ctypes.data, n, stats.ctypes.data, F1, F2,
+        msc.ctypes.data, p1.ctypes.data, vsc.ctypes.data, p2.ctypes.data, fsc.ctypes.data, fpv.ctypes.data,
+        C.byref(n1), C.byref(n2)), "msv_fwd_filter_batch")
     return {"msv_scores": msc, "passed_msv": p1.astype(bool), "vit_scores": vsc, "passed_vit": p2.astype(bool),
             "fwd_scores": fsc, "fwd_pvalues": fpv}
 
@@ -829,20 +714,13 @@ def score_grid(engines: Sequence[MSV_HMM], seqs: Sequence[str] | None = None, *,
     is written by the kernels directly); page-locked `codes` are read in place."""
     if not engines:
         raise ValueError("score_grid needs at least one profile")
-    if seqs is not None:
-        codes, offsets = pack_sequences(seqs)
-    codes = np.ascontiguousarray(codes, np.uint8)
-    offsets = np.ascontiguousarray(offsets, np.uint64)
-    n = len(offsets) - 1
+    codes, offsets, n = _batch(seqs, codes, offsets)
     if out is None:
         out = np.zeros((len(engines), n), np.float32)
     elif out.dtype != np.float32 or out.shape != (len(engines), n) or not out.flags.c_contiguous:
         raise ValueError("out must be a C-contiguous float32 array of shape (len(engines), n)")
-    st = _native.lib().msv_score_grid(_handles(engines), len(engines), codes.ctypes.data if codes.size else None,
-                                      offsets.ctypes.data, n, out.ctypes.data, None)
-    if st == _native.MSV_ERR_BAD_RESIDUE:
-        raise IndexError("residue outside the 20 amino acids")
-    check(st, "msv_score_grid")
+    _check_residues(_native.lib().msv_score_grid(_handles(engines), len(engines), _ptr(codes), offsets.ctypes.data, n,
+                                                 out.ctypes.data, None), "msv_score_grid")
     return out
 
 
@@ -869,17 +747,11 @@ def score_batch_multi(engines: Sequence[MSV_HMM], seqs: Sequence[str] | None = N
     residue-balanced contiguous shards scored concurrently, scores in input order."""
     if not engines:
         raise ValueError("score_batch_multi needs at least one engine")
-    if seqs is not None:
-        codes, offsets = pack_sequences(seqs)
-    codes = np.ascontiguousarray(codes, np.uint8)
-    offsets = np.ascontiguousarray(offsets, np.uint64)
-    n = len(offsets) - 1
+    codes, offsets, n = _batch(seqs, codes, offsets)
     out = np.zeros(n, np.float32)
-    st = _native.lib().msv_score_batch_multi(_handles(engines), len(engines), codes.ctypes.data if codes.size else None,
-                                             offsets.ctypes.data, n, out.ctypes.data)
-    if st == _native.MSV_ERR_BAD_RESIDUE:
-        raise IndexError("residue outside the 20 amino acids")
-    check(st, "msv_score_batch_multi")
+    _check_residues(_native.lib().msv_score_batch_multi(_handles(engines), len(engines), _ptr(codes),
+                                                        offsets.ctypes.data, n, out.ctypes.data),
+                    "msv_score_batch_multi")
     return out
 
 
@@ -899,17 +771,10 @@ class MultiGPU:
 
     def score_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
                     offsets: np.ndarray | None = None) -> np.ndarray:
-        if seqs is not None:
-            codes, offsets = pack_sequences(seqs)
-        codes = np.ascontiguousarray(codes, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        n = len(offsets) - 1
+        codes, offsets, n = _batch(seqs, codes, offsets)
         out = np.zeros(n, np.float32)
-        st = _native.lib().msv_multi_score_batch(self._m, codes.ctypes.data if codes.size else None,
-                                                 offsets.ctypes.data, n, out.ctypes.data)
-        if st == _native.MSV_ERR_BAD_RESIDUE:
-            raise IndexError("residue outside the 20 amino acids")
-        check(st, "msv_multi_score_batch")
+        _check_residues(_native.lib().msv_multi_score_batch(self._m, _ptr(codes), offsets.ctypes.data, n,
+                                                            out.ctypes.data), "msv_multi_score_batch")
         return out
 
     def close(self):

@@ -9,8 +9,8 @@
 //     E = sum_k M(i,k) + D(i,k);  N *= loop;  J = J loop + E tEJ;  C = C loop + E tEC;  B = (N + J) move
 //
 // The shape is vit_kernel.hip's (one sequence per 64-lane wave, lane l holds the S consecutive states
-// l*S+1 .. l*S+S of M, I, D in VGPRs, wave-uniform residues in 64-row blocks, persistent grid with the first
-// sequence static and the later ones taken by one atomic, select / select_count, error bits).  What differs:
+// l*S+1 .. l*S+S of M, I, D in VGPRs, wave-uniform residues in 64-row blocks) on the same work queue
+// (seq_queue.h: persistent grid, select / select_count, error bits).  What differs:
 //   * float32 odds, rescaled by an exact power of two whenever the row's E passes 2^32 (E is wave-uniform, so the
 //     branch is scalar); the exponent is summed per sequence and comes back as e ln 2 in the score;
 //   * the D chain across lanes is a scan, not a lazy-F fix-point: every lane runs its S slots from an incoming 0,
@@ -26,18 +26,11 @@
 #include "fwd_host.h"
 #include "fwd_kernel.h"
 #include "msv_kernel.h"
+#include "seq_queue.h"
 
 namespace fwdk {
 
 namespace {
-
-__device__ __forceinline__ uint64_t u64first(uint64_t x) {
-    // (each half goes back to uint32_t before it is widened: the builtin returns int, and a low word with bit 31
-    // set would sign-extend over the high word)
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32)));
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
 
 // Lane l-1's value into lane l, 0 into lane 0: one DPP move across the wave (wave_shr:1, bound_ctrl off: the
 // lane without a source keeps `old`, which is 0).
@@ -73,19 +66,10 @@ __global__ __launch_bounds__(WAVES * 64) void fwd_kernel(const FwdArgs a) {
     __shared__ uint32_t exited_s;
     const int lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // the list's length, at most n: a device count beyond the batch is latched and clamped
-    uint64_t total = a.n;
-    if (a.select_count) {
-        const uint64_t c = *a.select_count;
-        if (c > a.n && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.errors, msvk::kErrBadOrder);
-        total = c < a.n ? c : a.n;
-    }
+    const uint64_t total = seqq::list_total(a);
     if (static_cast<uint64_t>(blockIdx.x) * WAVES >= total) {
         // no sequence for this workgroup (a device-count launch is sized for n): leave, counted like any other
-        if (threadIdx.x == 0 && atomicAdd(a.counter + 1, 1u) == gridDim.x - 1) {
-            atomicExch(a.counter, 0u);
-            atomicExch(a.counter + 1, 0u);
-        }
+        if (threadIdx.x == 0) seqq::count_leavers<1, 1>(a.counter);
         return;
     }
 
@@ -106,19 +90,9 @@ __global__ __launch_bounds__(WAVES * 64) void fwd_kernel(const FwdArgs a) {
     const uint32_t nwaves = gridDim.x * WAVES;
     uint32_t item = blockIdx.x * WAVES + wave;
     while (item < total) {
-        const uint32_t s = __builtin_amdgcn_readfirstlane(a.select ? a.select[item] : item);
-        const uint64_t o0 = u64first(a.offsets[s < a.n ? s : 0]);
-        const uint64_t L = s < a.n ? u64first(a.offsets[s + 1]) - o0 : 0;
-        if (s >= a.n) {
-            if (lane == 0) atomicOr(a.errors, msvk::kErrBadOrder);  // reported, never dereferenced
-        } else if (L == 0) {
-            if (lane == 0) a.scores[s] = -__builtin_inff();
-        } else if (L >= a.lentab_n) {
-            if (lane == 0) {
-                a.scores[s] = __uint_as_float(0x7fc00000u);
-                atomicOr(a.errors, msvk::kErrTooLong);
-            }
-        } else {
+        uint32_t s;
+        uint64_t o0, L;
+        if (seqq::take(a, item, lane, &s, &o0, &L)) {
             const float2 lm = a.lentab[L];
             const float loop = lm.x, move = lm.y;
             // everything a sequence carries starts here: M, I, D, the specials and the scale's exponent
@@ -242,10 +216,7 @@ __global__ __launch_bounds__(WAVES * 64) void fwd_kernel(const FwdArgs a) {
     // atomic per workgroup, by its last wave, counted in LDS)
     if (lane == 0) {
         __threadfence();
-        if (atomicAdd(&exited_s, 1u) == WAVES - 1 && atomicAdd(a.counter + 1, 1u) == gridDim.x - 1) {
-            atomicExch(a.counter, 0u);
-            atomicExch(a.counter + 1, 0u);
-        }
+        if (atomicAdd(&exited_s, 1u) == WAVES - 1) seqq::count_leavers<1, 1>(a.counter);
     }
 }
 

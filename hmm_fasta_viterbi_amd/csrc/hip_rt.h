@@ -1,7 +1,7 @@
-// hip_rt.h -- the host device layer's HIP plumbing, shared by msv_device.cpp, vit_device.cpp,
-// msv_multi.cpp and the host half of fasta_device.hip: the device guard, the status mapping and its
-// return-on-error macro, move-only owners of device buffers, pinned buffers, streams and events, the checks
-// every host entry point opens with, and the staging of one host batch (CsrStaging).
+// hip_rt.h -- the host device layer's HIP plumbing, shared by msv_device.cpp, msv_multi.cpp, the host half of
+// fasta_device.hip and, through stage_profile.h, the Viterbi and Forward layers: the device guard, the status
+// mapping and its return-on-error macro, move-only owners of device buffers, pinned buffers, streams and events,
+// the checks every host entry point opens with, and the staging of one host batch (CsrStaging).
 //
 // The owners never switch devices and never synchronise on their own (the one exception is documented at
 // DeviceBuffer::replace_with): whoever destroys or shrinks one does so with its device current and with

@@ -1,5 +1,5 @@
 // launch_ring.h -- launch slots of one device profile (host side), shared by the MSV profile
-// (msv_device.cpp) and the Viterbi profile (vit_device.cpp).
+// (msv_device.cpp) and the Viterbi and Forward profiles (stage_profile.h).
 //
 // A persistent kernel takes its work from a device counter pair {next index, waves left} that its last
 // wave puts back to zero.  Two launches of one profile that overlap on different streams must not

@@ -1,24 +1,19 @@
 // vit_device.cpp -- C-ABI of the Viterbi stage (msv.h) on the HIP runtime.
 //
 // The reference parses insert emissions, transitions and STATS LOCAL VITERBI (Profile_HMM.cpp:86-87,
-// 107-120) and never scores with them.  A msv_vit_profile holds the kernel-layout tables of one compiled
-// variant (vit_kernel.hip), its own per-length {tr_loop, tr_move} table (host logf, MSV_HMM.cpp:59-64)
-// and self-resetting dequeue counters (one pair per launch slot, launch_ring.h, so one profile may be
-// driven from several streams at once); a batch -- typically the MSV filter's survivors, selected on the
-// device -- is one persistent launch.
+// 107-120) and never scores with them.  A msv_vit_profile is a stage profile (stage_profile.h: tables, length
+// table, launch slots, streams, error words) of one compiled variant of vit_kernel.hip / vit_team.hip, with
+// log-score tables and a host-logf {tr_loop, tr_move} table (MSV_HMM.cpp:59-64); a batch -- typically the MSV
+// filter's survivors, selected on the device -- is one persistent launch.  The entry points are their argument
+// checks and one call into stage_profile.h; what is only the Viterbi stage's stands here.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <limits>
-#include <new>
 #include <vector>
 
 #include "hip_rt.h"
 #include "host_cpu.h"
-#include "launch_ring.h"
 #include "msv.h"
 #include "msv_kernel.h"
 #include "vit_kernel.h"
@@ -28,6 +23,8 @@ using msvrt::csr_extent;
 using msvrt::DeviceBuffer;
 using msvrt::DeviceGuard;
 using msvrt::hip_status;
+using stagedev::kHostErrWord;
+using stagedev::kSelWord;
 
 // table_layout.cpp builds the tables without vit_kernel.h
 static_assert(vitk::kRows == 20 && vitk::kTransitions == 7 && vitk::kLanes == 64, "table_layout.cpp's shape");
@@ -35,79 +32,26 @@ static_assert(vitk::MM_IN == 0 && vitk::IM_IN == 1 && vitk::DM_IN == 2 && vitk::
                   vitk::MD_IN == 5 && vitk::DD_IN == 6,
               "table_layout.cpp's slot arrays");
 
-using vitdev::kErrWord;
-using vitdev::kHostErrWord;
-using vitdev::kSelWord;
-using vitdev::kWords;
-using vitdev::read_errors;
-
-namespace vitdev {
-
-msv_status err_status(uint32_t err) {
-    if (err & msvk::kErrBadResidue) return MSV_ERR_BAD_RESIDUE;
-    if (err & msvk::kErrTooLong) return MSV_ERR_SEQUENCE_TOO_LONG;
-    if (err & msvk::kErrBadOrder) return MSV_ERR_INVALID_ARGUMENT;  // a survivors entry outside the batch
-    if (err & msvk::kErrTeamHang) return MSV_ERR_HIP;
-    return err ? MSV_ERR_INVALID_ARGUMENT : MSV_OK;
-}
-
-}  // namespace vitdev
-
 namespace {
-
-constexpr uint32_t kDefaultMaxLength = 131072;
-// The automatic choice covering `states`: among the variants marked `pick` (one per S and insert mode, by
-// measurement), the fewest slots.  Informative insert scores need an isc variant.
-const vitk::VitVariant* pick_variant(uint32_t states, bool isc) {
-    int n = 0;
-    const vitk::VitVariant* all = vitk::vit_variants(&n);
-    const vitk::VitVariant* best = nullptr;
-    for (int i = 0; i < n; ++i) {
-        const vitk::VitVariant& v = all[i];
-        if (!v.pick || v.isc != isc || static_cast<uint32_t>(v.states()) < states) continue;
-        if (!best || v.states() < best->states()) best = &v;
-    }
-    return best;
-}
 
 // Lays the variant's tables out (msv_host::vit_tables) and uploads them, all three or none: each goes into a
 // fresh buffer, and the profile adopts them together.
 msv_status install(msv_vit_profile* p, const vitk::VitVariant* v) {
     const msv_host::VitTables t = msv_host::vit_tables(p->msc.data(), p->isc_tab.data(), p->tsc.data(), p->model_length,
                                                        v->S, v->team, p->isc);
-    auto upload = [](DeviceBuffer<float2>& d, const std::vector<float>& pairs) {
-        return d.replace_with(reinterpret_cast<const float2*>(pairs.data()), pairs.size() / 2);
-    };
     DeviceBuffer<float2> de, di, dt;
     hipError_t e;
-    if ((e = upload(de, t.et)) != hipSuccess || (e = upload(dt, t.tt)) != hipSuccess ||
-        (p->isc && (e = upload(di, t.it)) != hipSuccess))
+    if ((e = stagedev::upload_pairs(de, t.et)) != hipSuccess || (e = stagedev::upload_pairs(dt, t.tt)) != hipSuccess ||
+        (p->isc && (e = stagedev::upload_pairs(di, t.it)) != hipSuccess))
         return hip_status(e);
-    int blocks = 0;
-    if ((e = msvrt::resident_blocks(p->device, v->fn, v->waves * 64, &blocks)) != hipSuccess) return hip_status(e);
-    // the previous tables may still be read by a launch in flight on any stream
-    if (p->d_etab || p->d_ttab) (void)hipDeviceSynchronize();
-    p->d_etab = std::move(de);
-    p->d_itab = std::move(di);
-    p->d_ttab = std::move(dt);
-    p->v = v;
-    p->blocks = static_cast<uint32_t>(std::max(1, blocks));
-    return MSV_OK;
+    const msv_status s = stagedev::adopt_tables(p, v->fn, v->waves * 64, de, di, dt);
+    if (s == MSV_OK) p->v = v;
+    return s;
 }
 
-hipStream_t stream_of(const msv_vit_profile* p, void* stream) {
-    return stream ? static_cast<hipStream_t>(stream) : static_cast<hipStream_t>(p->stream);
-}
-
-// Every launch takes the next counter slot (a slot whose previous launch ran on another stream is reused
-// only after it: launch_ring.h), so launches of one profile on several streams never share a counter.
-// `errors` is the word the kernel latches its error bits into (device launches: kErrWord; host calls:
-// kHostErrWord).
 msv_status launch(msv_vit_profile* p, const uint8_t* d_residues, const uint64_t* d_offsets, uint64_t n,
                   const uint32_t* d_select, const uint32_t* d_select_count, float* d_scores, hipStream_t st,
-                  uint32_t* errors, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
-    if (n == 0) return MSV_OK;
-    if (n >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
+                  uint32_t* errors) {
     vitk::VitArgs a{};
     a.etab = p->d_etab;
     a.itab = p->d_itab ? p->d_itab.get() : p->d_etab.get();
@@ -125,122 +69,52 @@ msv_status launch(msv_vit_profile* p, const uint8_t* d_residues, const uint64_t*
     a.tr_E_C = p->tr_E_C;
     a.tr_E_J = p->tr_E_J;
     a.stamps = p->d_stamps;
-    // one wave (team) per sequence: no more workgroups than the items need (a device count is bounded by n)
-    const uint64_t per_block = static_cast<uint64_t>(p->v->sequences_per_block());
-    const uint64_t need = (n + per_block - 1) / per_block;
-    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(p->blocks, need));
-    if (!start && !stop && (p->time_start || p->time_stop)) {
-        start = p->time_start;
-        stop = p->time_stop;
-        p->time_start = p->time_stop = nullptr;
-    }
-    // a slot's counters are put back to zero by the last wave of every launch; a failed launch may leave
-    // them dirty, so the slot's next launch resets them explicitly (LaunchRing::run)
-    const bool lazy = st == p->stream || (p->bound && st == p->bound);
-    MSV_HIP(p->kernels.run(st, lazy, p->d_words.get(), 2, [&](uint32_t* counter) {
-        a.counter = counter;
-        return vitk::vit_launch(*p->v, blocks, a, st, start, stop);
-    }));
-    return MSV_OK;
+    // one wave (team) per sequence
+    return stagedev::run(p, st, n, static_cast<uint64_t>(p->v->sequences_per_block()),
+                         [&](uint32_t blocks, uint32_t* counter) {
+                             a.counter = counter;
+                             const hipEvent_t start = p->time_start, stop = p->time_stop;  // this launch's only
+                             p->time_start = p->time_stop = nullptr;
+                             return vitk::vit_launch(*p->v, blocks, a, st, start, stop);
+                         });
 }
 
 }  // namespace
 
-namespace vitdev {
-
-// Reads (and clears when set) one error word of the profile on `st`, synchronously.
-msv_status read_errors(msv_vit_profile* p, int word, hipStream_t st) {
-    uint32_t err = 0;
-    MSV_HIP(hipMemcpyAsync(&err, p->d_words + word, sizeof(err), hipMemcpyDeviceToHost, st));
-    MSV_HIP(hipStreamSynchronize(st));
-    if (err) {
-        MSV_HIP(hipMemsetAsync(p->d_words + word, 0, sizeof(uint32_t), st));
-        MSV_HIP(hipStreamSynchronize(st));
-    }
-    return err_status(err);
-}
-
-}  // namespace vitdev
-
 extern "C" {
 
-void msv_vit_profile_destroy(msv_vit_profile* p) {
-    if (!p) return;
-    DeviceGuard g(p->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-}
+void msv_vit_profile_destroy(msv_vit_profile* p) { stagedev::close(p); }
 
 msv_status msv_vit_profile_reserve_length(msv_vit_profile* p, uint64_t max_length) {
-    if (!p) return MSV_ERR_INVALID_ARGUMENT;
-    if (max_length >= (1ull << 31)) return MSV_ERR_SEQUENCE_TOO_LONG;
-    const uint32_t need = static_cast<uint32_t>(max_length) + 1;
-    if (need <= p->lentab_n) return MSV_OK;
-    DeviceGuard g(p->device);
-    if (!g.ok) return MSV_ERR_NO_DEVICE;
-    const uint32_t n = std::max(need, p->lentab_n * 2);
-    std::vector<float2> host(n);
-    for (uint32_t L = 0; L < n; ++L) msv_sequence_transitions(L, &host[L].x, &host[L].y);  // MSV_HMM.cpp:59-64
-    MSV_HIP(p->d_lentab.replace_with(host.data(), n));
-    p->lentab_n = n;
-    return MSV_OK;
+    return stagedev::reserve_length(p, max_length, [](uint32_t L, float2& t) {
+        msv_sequence_transitions(L, &t.x, &t.y);  // MSV_HMM.cpp:59-64
+    });
 }
 
 msv_status msv_vit_profile_create(int device, const float* match_scores, const float* insert_scores,
                                   const float* transition_scores, uint32_t model_length, float tr_B_Mk, float tr_E_C,
                                   float tr_E_J, msv_vit_profile** out) {
-    if (!match_scores || !transition_scores || !out || model_length < 2) return MSV_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    // The kernel leaves D(LENG) out of E, exact only while every transition it reads (nodes 1 .. LENG-1,
-    // install) is <= 0 (then every D is bounded by an M of its row); log-probabilities always are.
-    for (size_t k = 1; k + 1 < model_length; ++k)
-        for (int t = 0; t < 7; ++t)
-            if (!(transition_scores[k * 7 + t] <= 0.0f)) return MSV_ERR_INVALID_ARGUMENT;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MSV_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return MSV_ERR_NO_DEVICE;
-    const vitk::VitVariant* v = pick_variant(model_length - 1, insert_scores != nullptr);
+    msv_status s = stagedev::check_model(match_scores, transition_scores, model_length, out);
+    if (s == MSV_OK) s = stagedev::check_device(device);
+    if (s != MSV_OK) return s;
+    // among the variants marked `pick` (one per S and insert mode, by measurement)
+    const vitk::VitVariant* v = stagedev::pick(vitk::vit_variants, model_length - 1, insert_scores != nullptr,
+                                               [](const vitk::VitVariant& x) { return x.pick; });
     if (!v) return MSV_ERR_UNSUPPORTED_MODEL;
-    DeviceGuard g(device);
-    if (!g.ok) return MSV_ERR_NO_DEVICE;
-    auto* p = new (std::nothrow) msv_vit_profile;
-    if (!p) return MSV_ERR_OUT_OF_MEMORY;
-    p->device = device;
-    p->model_length = model_length;
-    p->isc = insert_scores != nullptr;
-    p->tr_B_Mk = tr_B_Mk;
-    p->tr_E_C = tr_E_C;
-    p->tr_E_J = tr_E_J;
-    const size_t M = model_length;
-    p->msc.assign(match_scores, match_scores + 20 * M);
-    if (insert_scores) p->isc_tab.assign(insert_scores, insert_scores + 20 * M);
-    p->tsc.assign(transition_scores, transition_scores + 7 * M);
-    hipError_t e;
-    if ((e = p->stream.create(hipStreamNonBlocking)) != hipSuccess ||
-        (e = p->kernels.create_events()) != hipSuccess || (e = p->d_words.reserve(kWords)) != hipSuccess ||
-        (e = hipMemset(p->d_words, 0, kWords * sizeof(uint32_t))) != hipSuccess) {
-        msv_vit_profile_destroy(p);
-        return hip_status(e);
-    }
-    msv_status s = install(p, v);
-    if (s == MSV_OK) s = msv_vit_profile_reserve_length(p, kDefaultMaxLength - 1);
-    if (s != MSV_OK) {
-        msv_vit_profile_destroy(p);
-        return s;
-    }
-    *out = p;
-    return MSV_OK;
+    return stagedev::open(device, match_scores, insert_scores, transition_scores, model_length, out,
+                          [&](msv_vit_profile* p) {
+                              p->tr_B_Mk = tr_B_Mk;
+                              p->tr_E_C = tr_E_C;
+                              p->tr_E_J = tr_E_J;
+                              const msv_status si = install(p, v);
+                              return si == MSV_OK
+                                         ? msv_vit_profile_reserve_length(p, stagedev::kDefaultMaxLength - 1)
+                                         : si;
+                          });
 }
 
 msv_status msv_vit_profile_create_from_hmm(int device, const msv_hmm* hmm, int insert_mode, msv_vit_profile** out) {
-    if (!hmm || !out) return MSV_ERR_INVALID_ARGUMENT;
-    const size_t M = msv_hmm_model_length(hmm);
-    std::vector<float> msc(20 * M), isc(20 * M), tsc(7 * M);
-    float b, c, j;
-    msv_status s = msv_hmm_viterbi_scores(hmm, insert_mode, msc.data(), isc.data(), tsc.data(), &b, &c, &j);
-    if (s != MSV_OK) return s;
-    return msv_vit_profile_create(device, msc.data(), insert_mode == MSV_INSERTS_LOG_ODDS ? isc.data() : nullptr,
-                                  tsc.data(), static_cast<uint32_t>(M), b, c, j, out);
+    return stagedev::create_from_hmm(device, hmm, insert_mode, out, msv_vit_profile_create);
 }
 
 msv_status msv_vit_profile_describe(const msv_vit_profile* p, msv_vit_info* out) {
@@ -266,55 +140,22 @@ msv_status msv_vit_profile_describe(const msv_vit_profile* p, msv_vit_info* out)
     return MSV_OK;
 }
 
-int msv_vit_variant_count(void) {
-    int n = 0;
-    vitk::vit_variants(&n);
-    return n;
-}
+int msv_vit_variant_count(void) { return stagedev::variant_count(vitk::vit_variants); }
 
-const char* msv_vit_variant_name(int i) {
-    int n = 0;
-    const vitk::VitVariant* all = vitk::vit_variants(&n);
-    return (i >= 0 && i < n) ? all[i].name : "";
-}
+const char* msv_vit_variant_name(int i) { return stagedev::variant_name(vitk::vit_variants, i); }
 
 msv_status msv_vit_profile_set_variant(msv_vit_profile* p, const char* name) {
-    if (!p || !name) return MSV_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    const vitk::VitVariant* all = vitk::vit_variants(&n);
-    for (int i = 0; i < n; ++i)
-        if (std::strcmp(all[i].name, name) == 0) {
-            if (all[i].isc != p->isc || static_cast<uint32_t>(all[i].states()) < p->model_length - 1)
-                return MSV_ERR_UNSUPPORTED_MODEL;
-            DeviceGuard g(p->device);
-            if (!g.ok) return MSV_ERR_NO_DEVICE;
-            return install(p, &all[i]);
-        }
-    return MSV_ERR_INVALID_ARGUMENT;
+    return stagedev::set_variant(p, vitk::vit_variants, name, install);
 }
 
 msv_status msv_vit_score_batch_device(msv_vit_profile* p, const uint8_t* d_residues, uint64_t residues_len,
                                       const uint64_t* d_offsets, uint64_t n, const uint32_t* d_select,
                                       const uint32_t* d_select_count, float* d_scores, void* stream) {
-    if (!p || (n && (!d_offsets || !d_scores))) return MSV_ERR_INVALID_ARGUMENT;
-    if (n && residues_len && !d_residues) return MSV_ERR_INVALID_ARGUMENT;
-    if (d_select_count && !d_select) return MSV_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(p->device);
-    if (!g.ok) return MSV_ERR_NO_DEVICE;
-    return launch(p, d_residues, d_offsets, n, d_select, d_select_count, d_scores, stream_of(p, stream),
-                  p->d_words + kErrWord);
+    return stagedev::score_batch_device(p, d_residues, residues_len, d_offsets, n, d_select, d_select_count, d_scores,
+                                        stream, launch);
 }
 
-msv_status msv_vit_profile_bind_stream(msv_vit_profile* p, void* stream) {
-    if (!p) return MSV_ERR_INVALID_ARGUMENT;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (st == p->bound) return MSV_OK;
-    DeviceGuard g(p->device);
-    if (!g.ok) return MSV_ERR_NO_DEVICE;
-    if (p->bound) MSV_HIP(p->kernels.flush(p->bound));  // the old stream loses its guarantee
-    p->bound = st;
-    return MSV_OK;
-}
+msv_status msv_vit_profile_bind_stream(msv_vit_profile* p, void* stream) { return stagedev::bind_stream(p, stream); }
 
 // Diagnostic (bench.py): the next launch updates these two HIP events with its own start and end
 // (hipExtLaunchKernel), so a timed launch adds no marker packets to its stream.  Not in msv.h.
@@ -333,36 +174,11 @@ msv_status msv_vit_debug_set_stamps(msv_vit_profile* p, uint64_t* d_stamps) {
     return MSV_OK;
 }
 
-msv_status msv_vit_profile_check(msv_vit_profile* p, void* stream) {
-    if (!p) return MSV_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(p->device);
-    if (!g.ok) return MSV_ERR_NO_DEVICE;
-    return read_errors(p, kErrWord, stream_of(p, stream));
-}
+msv_status msv_vit_profile_check(msv_vit_profile* p, void* stream) { return stagedev::check(p, stream); }
 
 msv_status msv_vit_score_batch(msv_vit_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
                                float* scores, void* stream) {
-    if (!p || (n && (!offsets || !scores))) return MSV_ERR_INVALID_ARGUMENT;
-    if (n == 0) return MSV_OK;
-    uint64_t longest = 0, total = 0;
-    msv_status s = csr_extent(offsets, n, &longest, &total);
-    if (s != MSV_OK) return s;
-    if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(p->device);
-    if (!g.ok) return MSV_ERR_NO_DEVICE;
-    s = msv_vit_profile_reserve_length(p, longest);
-    if (s != MSV_OK) return s;
-    hipStream_t st = stream_of(p, stream);
-    msvrt::CsrStaging& sg = p->staged;
-    MSV_HIP(sg.d_scores.reserve(n));
-    // an early error return leaves no copy queued that reads the pinned offsets (rewritten by the next call)
-    msvrt::StreamDrain drain(st);
-    MSV_HIP(sg.upload(residues, offsets, 0, n, true, st, st));
-    s = launch(p, sg.d_res, sg.d_off, n, nullptr, nullptr, sg.d_scores, st, p->d_words + kHostErrWord);
-    if (s != MSV_OK) return s;
-    MSV_HIP(hipMemcpyAsync(scores, sg.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    drain.disarm();
-    return read_errors(p, kHostErrWord, st);  // synchronises
+    return stagedev::score_batch_host(p, residues, offsets, n, scores, stream, msv_vit_profile_reserve_length, launch);
 }
 
 msv_status msv_filter_select_device(int device, const float* d_scores, const uint64_t* d_offsets,
@@ -425,20 +241,13 @@ msv_status msv_vit_filter_batch(msv_profile* msv, msv_vit_profile* vit, const ui
     MSV_HIP(hipMemcpyAsync(msv_scores, vit->d_msc_out, n * sizeof(float), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipMemcpyAsync(vit_scores, sg.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipMemcpyAsync(&count, vit->d_words + kSelWord, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    std::vector<uint32_t> sel;
     MSV_HIP(hipStreamSynchronize(st));
     drain.disarm();
-    if (count) {
-        sel.resize(count);
-        MSV_HIP(hipMemcpyAsync(sel.data(), vit->d_sel, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        MSV_HIP(hipStreamSynchronize(st));
-    }
-    std::fill(passed, passed + n, static_cast<uint8_t>(0));
-    for (uint32_t x : sel) passed[x] = 1;
+    if ((s = stagedev::survivor_mask(st, count, vit->d_sel, passed, n)) != MSV_OK) return s;
     *n_passed = count;
     // both stages' words are read, so each call clears its own bits (a bad residue in a survivor latches both)
     s = msv_profile_check(msv, st);
-    const msv_status vs = read_errors(vit, kHostErrWord, st);
+    const msv_status vs = stagedev::read_errors(vit, kHostErrWord, st);
     return s != MSV_OK ? s : vs;
 }
 

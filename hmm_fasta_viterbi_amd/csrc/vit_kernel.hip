@@ -29,7 +29,7 @@
 //     beats J + loop; C is a per-lane partial, its 64-lane max taken once per sequence;
 //   * match scores staged in LDS ([20][S/2][64] float2: each ds_read_b64 of a wave is contiguous) and the
 //     7 transition arrays in VGPRs, or (large models) transitions in LDS and match scores from L2;
-//   * persistent grid, first sequence static, then one atomic per sequence; the counter resets itself.
+//   * persistent grid on the work queue of seq_queue.h, which fwd_kernel.hip and in part vit_team.hip share.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "msv_kernel_impl.h"
+#include "seq_queue.h"
 #include "vit_kernel.h"
 
 namespace vitk {
@@ -50,13 +51,6 @@ constexpr int kEarlyD = 8;  // slots of the unconditional first lazy-F pass befo
 constexpr int kEarlyHopStates = 8;
 
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
-__device__ __forceinline__ uint64_t u64first(uint64_t x) {
-    // (the builtin returns int: each half goes back to uint32_t before it is widened, or a low word with bit 31
-    // set -- a residue offset in [2^31, 2^32) -- would sign-extend over the high word)
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32)));
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
 
 // Lane l-1's value into lane l (64 lanes); lane 0 keeps `old`'s lane 0, which its caller keeps at -inf
 // (the dummy column k = 0).  One DPP move across the whole wave (wave_shr:1, bound_ctrl off: the lane
@@ -104,22 +98,12 @@ __global__ __launch_bounds__(WAVES * 64) void vit_kernel(const VitArgs a) {
     const int lane = threadIdx.x & 63;
     // (readfirstlane: wave-uniform, so the sequence, its bounds and every branch on them are scalar)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // the list's length, at most n: a device count beyond the batch is latched (kErrBadOrder) and clamped, so no
-    // wave reads the list past its n entries
-    uint64_t total = a.n;
-    if (a.select_count) {
-        const uint64_t c = *a.select_count;
-        if (c > a.n && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.errors, msvk::kErrBadOrder);
-        total = c < a.n ? c : a.n;
-    }
+    const uint64_t total = seqq::list_total(a);
     if (static_cast<uint64_t>(blockIdx.x) * WAVES >= total) {
         // no sequence for this workgroup (a device-count launch is sized for n, the count may be far less:
         // cfg2's 260 survivors of 10,000): no first item, and none of the queue's (it starts at the grid's
         // wave count) -- leave without staging the tables, counted like any other workgroup
-        if (threadIdx.x == 0 && atomicAdd(a.counter + 1, 1u) == gridDim.x - 1) {
-            atomicExch(a.counter, 0u);
-            atomicExch(a.counter + 1, 0u);
-        }
+        if (threadIdx.x == 0) seqq::count_leavers<1, 1>(a.counter);
         return;
     }
 
@@ -159,20 +143,9 @@ __global__ __launch_bounds__(WAVES * 64) void vit_kernel(const VitArgs a) {
     const bool few = total <= nwaves;  // wave-uniform: a latency-bound launch (no wave takes a second sequence)
     uint32_t item = blockIdx.x * WAVES + wave;
     while (item < total) {
-        const uint32_t s = __builtin_amdgcn_readfirstlane(a.select ? a.select[item] : item);
-        const uint64_t o0 = u64first(a.offsets[s < a.n ? s : 0]);
-        const uint64_t L = s < a.n ? u64first(a.offsets[s + 1]) - o0 : 0;
-        if (s >= a.n) {
-            // a survivors entry outside the batch (a caller's list): reported, never dereferenced
-            if (lane == 0) atomicOr(a.errors, msvk::kErrBadOrder);
-        } else if (L == 0) {
-            if (lane == 0) a.scores[s] = NINF;  // C_0 = -inf, as MSV_HMM.cpp:86,112
-        } else if (L >= a.lentab_n) {
-            if (lane == 0) {
-                a.scores[s] = __uint_as_float(0x7fc00000u);
-                atomicOr(a.errors, msvk::kErrTooLong);
-            }
-        } else {
+        uint32_t s;
+        uint64_t o0, L;
+        if (seqq::take(a, item, lane, &s, &o0, &L)) {
             const float2 lm = a.lentab[L];
             const float loop = lm.x, move = lm.y;
             float M[S], I[S], D[S];
@@ -455,10 +428,7 @@ __global__ __launch_bounds__(WAVES * 64) void vit_kernel(const VitArgs a) {
     // profiles/r05_ab_wg_exit.jsonl; the MSV and team kernels were neutral / +1.3% and keep a count per wave)
     if (lane == 0) {
         __threadfence();
-        if (atomicAdd(&exited_s, 1u) == WAVES - 1 && atomicAdd(a.counter + 1, 1u) == gridDim.x - 1) {
-            atomicExch(a.counter, 0u);
-            atomicExch(a.counter + 1, 0u);
-        }
+        if (atomicAdd(&exited_s, 1u) == WAVES - 1) seqq::count_leavers<1, 1>(a.counter);
     }
 }
 

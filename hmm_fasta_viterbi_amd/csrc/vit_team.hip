@@ -6,6 +6,7 @@
 //     I(i,k) = max(M'(k)+tMI, I'(k)+tII)                            (isc = 0: HMMER3's insert scores)
 //     D(i,k) = max(M(k-1)+tMD, D(k-1)+tDD)                           <- within the row
 //     E = max_k M(i,k);  J, C, N, B as MSV_HMM.cpp:100-112
+// The work queue is seq_queue.h's with a team as the worker; a team takes its next item late and counts its waves.
 //
 // Why teams.  With one sequence per 64-lane wave, a lane holds S = LENG/64 states of M, I, D plus the
 // seven per-state transition scores: 10 S registers.  At S = 22 (1400.hmm) two waves fit a SIMD and at
@@ -42,6 +43,7 @@
 #include <hip/hip_runtime.h>
 
 #include "msv_kernel_impl.h"
+#include "seq_queue.h"
 #include "vit_kernel.h"
 
 namespace vitk {
@@ -86,13 +88,7 @@ __device__ __forceinline__ v2f lds_read2(const float2* p) { return *(const volat
 __device__ __forceinline__ void lds_write4(float4* p, v4f v) { *(volatile LDS_AS v4f*)(p) = v; }
 __device__ __forceinline__ void lds_write2(float2* p, v2f v) { *(volatile LDS_AS v2f*)(p) = v; }
 __device__ __forceinline__ uint32_t ufirst(float x) { return __builtin_amdgcn_readfirstlane(__float_as_uint(x)); }
-__device__ __forceinline__ uint64_t u64first(uint64_t x) {
-    // (the builtin returns int: each half goes back to uint32_t before it is widened, or a low word with bit 31
-    // set -- a residue offset in [2^31, 2^32) -- would sign-extend over the high word)
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32)));
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
+using seqq::u64first;
 
 }  // namespace
 
@@ -118,21 +114,11 @@ __global__ __launch_bounds__(NT * W * 64) void vit_team_kernel(const VitArgs a) 
     __shared__ float4 tdm_s[LA == 2 ? C4 * VL : 1];
     __shared__ TeamX<W> tx_s[NT];
     const uint64_t t_entry = __builtin_amdgcn_s_memrealtime();  // (a.stamps only)
-    // the list's length, at most n: a device count beyond the batch is latched (kErrBadOrder) and clamped, so no
-    // wave reads the list past its n entries
-    uint64_t total = a.n;
-    if (a.select_count) {
-        const uint64_t c = *a.select_count;
-        if (c > a.n && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.errors, msvk::kErrBadOrder);
-        total = c < a.n ? c : a.n;
-    }
+    const uint64_t total = seqq::list_total(a);
     if (static_cast<uint64_t>(blockIdx.x) * NT >= total) {
         // no sequence for this workgroup (vit_kernel.hip: a device-count launch sized for n): leave at once,
         // counted as its NT * W waves
-        if (threadIdx.x == 0 && atomicAdd(a.counter + 1, static_cast<uint32_t>(NT * W)) == (gridDim.x - 1) * NT * W) {
-            atomicExch(a.counter, 0u);
-            atomicExch(a.counter + 1, 0u);
-        }
+        if (threadIdx.x == 0) seqq::count_leavers<NT * W, NT * W>(a.counter);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -546,10 +532,7 @@ __global__ __launch_bounds__(NT * W * 64) void vit_team_kernel(const VitArgs a) 
     // the last wave to finish resets the slot's counters for its next launch
     if (lane == 0) {
         __threadfence();
-        if (atomicAdd(a.counter + 1, 1u) == gridDim.x * NT * W - 1) {
-            atomicExch(a.counter, 0u);
-            atomicExch(a.counter + 1, 0u);
-        }
+        seqq::count_leavers<NT * W, 1>(a.counter);
     }
 }
 

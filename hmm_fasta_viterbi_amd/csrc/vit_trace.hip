@@ -18,12 +18,12 @@
 //     after lazy-F has converged -- so the bits are the serial DP's (msv_host::viterbi_trace_on_sequence);
 //   * E's argmax is a workgroup max, then the smallest k holding it (a workgroup min over the lanes' first
 //     matching slot); J, C, N, B are then computed by every lane alike, and lane 0 writes the row's record;
-//   * the grid is persistent: the first item is static, the rest come from one atomic per workgroup, and the
-//     last workgroup to leave puts the counter pair back to zero.
+//   * the grid is persistent, its queue seq_queue.h's with a workgroup as the worker (no select_count, no idle exit).
 // Rows never live in scratch: the row arrays are indexed by unrolled constants only.
 #include <hip/hip_runtime.h>
 
 #include "msv_kernel_impl.h"
+#include "seq_queue.h"
 #include "vit_kernel.h"
 #include "vit_trace.h"
 #include "vit_trace_plan.h"
@@ -44,12 +44,7 @@ using vitk::MM_IN;
 
 constexpr float NINF = -__builtin_inff();
 
-// (vit_kernel.hip's u64first: the builtin returns int, so each half goes back to uint32_t before it is widened)
-__device__ __forceinline__ uint64_t u64first(uint64_t x) {
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32)));
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
+using seqq::u64first;
 
 __device__ __forceinline__ float wave_max(float x) {
 #pragma unroll
@@ -241,10 +236,7 @@ __global__ __launch_bounds__(T * 64) void vit_trace_fill(const FillArgs a) {
     // the last workgroup to finish resets the counters for the next launch on this slot
     if (vl == 0) {
         __threadfence();
-        if (atomicAdd(a.counter + 1, 1u) == gridDim.x - 1) {
-            atomicExch(a.counter, 0u);
-            atomicExch(a.counter + 1, 0u);
-        }
+        seqq::count_leavers<1, 1>(a.counter);
     }
 }
 

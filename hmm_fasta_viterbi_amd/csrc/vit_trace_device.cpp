@@ -41,12 +41,9 @@ msv_status ensure_plan(msv_vit_profile* p) {
     const vittrace::Plan& pl = vittrace::kPlans[plan];
     const msv_host::VitTables tab = msv_host::vit_tables(p->msc.data(), p->isc_tab.data(), p->tsc.data(),
                                                          p->model_length, pl.S, pl.team, p->isc);
-    auto upload = [](msvrt::DeviceBuffer<float2>& d, const std::vector<float>& pairs) {
-        return d.replace_with(reinterpret_cast<const float2*>(pairs.data()), pairs.size() / 2);
-    };
-    MSV_HIP(upload(t.d_etab, tab.et));
-    MSV_HIP(upload(t.d_ttab, tab.tt));
-    if (p->isc) MSV_HIP(upload(t.d_itab, tab.it));
+    MSV_HIP(stagedev::upload_pairs(t.d_etab, tab.et));
+    MSV_HIP(stagedev::upload_pairs(t.d_ttab, tab.tt));
+    if (p->isc) MSV_HIP(stagedev::upload_pairs(t.d_itab, tab.it));
     int blocks = 0;
     MSV_HIP(msvrt::resident_blocks(p->device, vittrace::fill_kernel(plan), static_cast<int>(pl.lanes()), &blocks));
     MSV_HIP(t.t0.create(hipEventDefault));
@@ -98,7 +95,7 @@ msv_status run_chunk(msv_vit_profile* p, const uint32_t* sel, const uint64_t* by
     f.lentab = p->d_lentab;
     f.ws = t.d_ws;
     f.scores = t.d_scores;
-    f.errors = p->d_words + vitdev::kHostErrWord;
+    f.errors = p->d_words + stagedev::kHostErrWord;
     f.n_items = static_cast<uint32_t>(m);
     f.lentab_n = p->lentab_n;
     f.tr_B_Mk = p->tr_B_Mk;
@@ -245,7 +242,7 @@ msv_status msv_vit_trace_batch(msv_vit_profile* p, const uint8_t* residues, cons
     }  // (drained: every chunk has synchronised, or an error has)
     p->trace.d_ws.reset();  // the workspace is not kept between calls
     if (s != MSV_OK) return fail(s);
-    s = vitdev::read_errors(p, vitdev::kHostErrWord, st);
+    s = stagedev::read_errors(p, stagedev::kHostErrWord, st);
     if (s != MSV_OK && s != MSV_ERR_BAD_RESIDUE && s != MSV_ERR_SEQUENCE_TOO_LONG) return fail(s);
     *traces = out;
     return s;

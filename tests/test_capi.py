@@ -119,6 +119,24 @@ def test_viterbi_entry_points_validate_arguments():
     assert L.msv_vit_profile_bind_stream(None, None) == 1
 
 
+@pytest.mark.parametrize("prefix", ["msv_vit", "msv_fwd"])
+def test_stage_create_and_bind_validate_arguments(prefix):
+    """Both stages' create refuses a transition score that is not a log-probability (positive, or NaN) before
+    any device is touched, and bind_stream a NULL profile: status 1 (MSV_ERR_INVALID_ARGUMENT) from either."""
+    import numpy as np
+    L = _native.lib()
+    create, bind = getattr(L, prefix + "_profile_create"), getattr(L, prefix + "_profile_bind_stream")
+    M = 101
+    msc = np.zeros((20, M), np.float32)
+    tsc = np.full((M, 7), np.float32(np.log(np.float32(0.5))), np.float32)
+    p = C.c_void_p()
+    for bad in (0.25, np.nan):
+        tsc[5, 3] = bad  # node 5, i->m
+        assert create(0, msc.ctypes.data, None, tsc.ctypes.data, M, -8.0, -0.69, -0.69, C.byref(p)) == 1
+        assert not p.value
+    assert bind(None, None) == 1
+
+
 def test_info_struct_layouts_match_the_header(tmp_path):
     """The ctypes mirrors of msv_kernel_info / msv_vit_info (hmm_fasta_viterbi_amd/_native.py) have the C header's
     field offsets and sizes (gcc on include/msv.h), and both structs keep their round-4 prefix: fields are only

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Dump the gfx950 assembly of every MSV and Viterbi kernel translation unit into $1 (one .s per TU), for
+# Dump the gfx950 assembly of every MSV, Viterbi and Forward kernel translation unit into $1 (one .s per TU), for
 # instruction-for-instruction comparisons of a source change (tools/isa_compare.py).
 set -e
 OUT=${1:?usage: tools/isa_dump.sh OUTDIR}
@@ -15,4 +15,5 @@ done
 /opt/rocm/bin/hipcc $FLAGS "$HERE/vit_kernel.hip" -o "$OUT/vit_kernel.s" &
 /opt/rocm/bin/hipcc $FLAGS "$HERE/vit_team.hip" -o "$OUT/vit_team.s" &
 /opt/rocm/bin/hipcc $FLAGS "$HERE/vit_trace.hip" -o "$OUT/vit_trace.s" &
+/opt/rocm/bin/hipcc $FLAGS "$HERE/fwd_kernel.hip" -o "$OUT/fwd_kernel.s" &
 wait
