@@ -13,8 +13,11 @@ from hmm_fasta_viterbi_amd.synthetic import (concat_batches, gapped_homolog_batc
                                              write_hmm)
 from oracle_lib import bits, profile_path
 from state_batches import _csr, boundary_batch, edge_batch, tail_gapped_batch
+from test_viterbi_paths import lib_cpu
 from test_viterbi_trace_host import host_tables, stress_tables, tiny_cases
-from trace_check import F, assert_same, cpu_traces, profile_from_tables, tables_of, traces_lists, two_core_batch
+from trace_check import (F, assert_same, cpu_trace, cpu_traces, profile_from_tables, py_trace, quantised_model, rescore,
+                         tables_of, traces_lists, two_core_batch)
+from trace_ties import RULES, anchored_cases, d_takes_m_before_d, e_takes_the_smallest_k, prove
 
 pytestmark = pytest.mark.gpu
 
@@ -240,3 +243,119 @@ def test_filter_pipeline_align():
     assert path[0] == ("M", int(d0["k_from"]), int(d0["i_from"])) and len(path) == int(traces.domains_of(q)["ops_len"].sum())
     lines = traces.alignment(q, 0).split("\n")
     assert len(lines) == 3 and len(lines[0]) == len(lines[1]) == len(lines[2]) == int(d0["ops_len"])
+
+
+# ---- exact ties: every tie-break rule of msv.h at the lane, word and wave edges of every plan (trace_ties) ----------
+
+def plan_anchors(S, team, leng):
+    """Slot 0 of a lane in mid-wave (its left neighbour's values come through LDS), a lane's last slot, the second
+    pointer word of a 16-state lane, and for a team the last state of wave 0 and the first of waves 1 and 3."""
+    out = [S + 1, 2 * S]
+    if S > 8:
+        out.append(9)
+    if team > 1:
+        out += [64 * S, 64 * S + 1, 192 * S + 1]
+    assert max(out) < leng
+    return out
+
+
+def e_tie_sets(S, team, leng):
+    """Two slots of a lane; a lane's last slot and the next lane's slot 0; two lanes of a wave; wave 0 and wave 3;
+    the two ends; a three-way tie whose smallest node sits in a lower wave than the other two (given in falling order)."""
+    sets = [(S + 2, S + 5), (3 * S, 3 * S + 1), (2 * S + 3, 40 * S + 2), (1, leng)]
+    if team > 1:
+        sets += [(5 * S + 4, 192 * S + 7), (200 * S + 5, 193 * S + 2, 130 * S + 3)]
+    return sets
+
+
+def assert_gpu_takes_expected(case, what, plan=None):
+    """trace_batch gives the domains written out from the construction and the bits of their re-score; then, as a
+    separate statement, what the CPU trace gives."""
+    vit = profile_from_tables(*case.tables)
+    try:
+        if plan is not None:
+            assert vit.trace_describe()["plan"] == plan, what
+        batch = _csr([case.codes])
+        t = vit.trace_batch(codes=batch[0], offsets=batch[1])
+        got = traces_lists(t)[0]
+        assert got == case.expected, (what, got, case.expected, case.alternatives)
+        assert bits(t.scores[0]) == bits(rescore(*case.tables, case.codes, case.expected)), what
+        assert_same(t, [cpu_trace(*case.tables, case.codes)], what)
+    finally:
+        vit.close()
+
+
+@pytest.mark.parametrize("plan", range(len(PLANS)))
+def test_every_tie_break_rule_at_the_plan_edges(plan):
+    """A model of the plan's capacity; every builder case with its tied cell at each anchor of plan_anchors, at the
+    first and at the last node its rule allows; E ties inside a lane, across lanes and across waves; and a D tie
+    whose losing chain is longer than a lane and crosses a wave boundary (or, in the one-wave plan, two lanes), so
+    that the tied value is one that lazy-F propagated over more than one round."""
+    name, leng = PLANS[plan]
+    S, team = {"vit_trace_s8_w1": (8, 1), "vit_trace_s8_w4": (8, 4), "vit_trace_s16_w4": (16, 4)}[name]
+    assert leng == 64 * S * team
+    n = 0
+    for rule, k, case in anchored_cases(leng, plan_anchors(S, team, leng)):
+        prove(case, dp_score=lib_cpu)
+        assert_gpu_takes_expected(case, (name, rule, k), plan=name)
+        n += 1
+    assert n >= len(RULES) * 3
+    for ks in e_tie_sets(S, team, leng):
+        case = e_takes_the_smallest_k(leng, ks)
+        prove(case, dp_score=lib_cpu)
+        assert_gpu_takes_expected(case, (name, "E", ks), plan=name)
+    edge = 64 * S if team > 1 else 8 * S         # the chain ends three states past a wave (or lane) boundary
+    for k, chain in ((edge + 3, 2 * S + 5), (edge + S + 1, 2 * S + 1)):
+        case = d_takes_m_before_d(leng, k, chain=chain)
+        assert len(case.alternatives[0][0][4]) - 2 > S and case.alternatives[0][0][2] < edge - S
+        prove(case, dp_score=lib_cpu)
+        assert_gpu_takes_expected(case, (name, "D chain", k, chain), plan=name)
+
+
+# ---- quantised models: ties by the hundred, the GPU against the CPU trace and against py_trace ----------------------
+
+FUZZ = {24: ("vit_trace_s8_w1", 8, 3), 600: ("vit_trace_s8_w4", 8, 5), 2100: ("vit_trace_s16_w4", 16, 7)}
+
+
+def fuzz_model_and_batch(leng):
+    """A quantised model of LENG `leng` whose match scores take four values, and ~40 sequences of L 1..8 shuffled
+    with the edge lengths."""
+    seed = FUZZ[leng][2]
+    rng = np.random.Generator(np.random.PCG64(seed))
+    tables = quantised_model(rng, leng, leng == 600, leng != 24, step=0.5, emissions=(-1.5, -0.5, 0.5, 1.0), depth=1.5)
+    seqs = [rng.integers(0, 20, int(rng.integers(1, 9)), dtype=np.uint8) for _ in range(40)]
+    ec, eo = edge_batch(seed + 1)
+    seqs += [ec[int(eo[i]):int(eo[i + 1])] for i in range(len(eo) - 1)]
+    order = rng.permutation(len(seqs))
+    return tables, [seqs[int(i)] for i in order]
+
+
+def e_tie_spread(traces, S):
+    """(sequences with an on-path E tie over different lanes, ... over different waves), by py_trace's tied nodes."""
+    lanes = sum(any(len(set((nodes - 1) // S)) > 1 for nodes in t.e_tied) for t in traces)
+    waves = sum(any(len(set((nodes - 1) // (64 * S))) > 1 for nodes in t.e_tied) for t in traces)
+    return lanes, waves
+
+
+@pytest.mark.parametrize("leng", sorted(FUZZ))
+def test_quantised_models(leng):
+    """LENG 24 (one wave's first lanes), 600 (the boundary of waves 0 | 1 at 512 | 513 inside the model) and 2,100
+    (1,024 | 1,025).  trace_batch == the CPU trace == py_trace; and the batch is not vacuous: by py_trace alone, at
+    least 10 sequences tie in E over different lanes, in the team plans at least 5 over different waves."""
+    plan, S, _ = FUZZ[leng]
+    tables, seqs = fuzz_model_and_batch(leng)
+    ref = [py_trace(*tables, s) for s in seqs]
+    lanes, waves = e_tie_spread(ref, S)
+    tied = sum(t.tied for t in ref)
+    counts = f"LENG {leng}: {tied} of {len(seqs)} sequences tied on their path, {lanes} in E over lanes, {waves} over waves"
+    print(counts)
+    assert lanes >= 10 and (leng == 24 or waves >= 5), counts
+    vit = profile_from_tables(*tables)
+    try:
+        assert vit.trace_describe()["plan"] == plan
+        t = check(vit, *_csr(seqs), what=leng)
+        got = traces_lists(t)
+        for q, r in enumerate(ref):
+            assert bits(t.scores[q]) == bits(r.score) and got[q] == r.domains, (counts, q, got[q], r.domains)
+    finally:
+        vit.close()

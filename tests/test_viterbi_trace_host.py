@@ -1,7 +1,8 @@
 """The CPU Viterbi trace (msv_vit_cpu_trace) and the trace's host-only arithmetic (plans, back-pointer layout, chunk
 cuts), with no GPU.  Every traced path is checked by trace_check's independent checker: it must be a legal path
 of the model, and its float32 left-to-right re-score must have the bits of msv_vit_cpu_score -- on tiny models
-also the bits of the best path found by explicit enumeration (test_viterbi_paths.best_path)."""
+also the bits of the best path found by explicit enumeration (test_viterbi_paths.best_path).  Every tie-break rule
+of msv.h is pinned by trace_ties' exact-tie cases, and a third trace (trace_check.py_trace) by quantised models."""
 import ctypes as C
 import os
 import subprocess
@@ -15,7 +16,10 @@ from hmm_fasta_viterbi_amd.synthetic import gapped_homolog_batch
 from oracle_lib import GOLD, PROFILES, ROOT, bits, profile_path
 from state_batches import window_core, window_homolog_batch
 from test_viterbi_paths import best_path, lib_cpu, random_model
-from trace_check import F, MM, MI, MD, IM, DM, DD, check_legal, cpu_trace, cpu_traces, rescore, two_core_batch
+from trace_check import (F, MM, MI, MD, IM, DM, DD, check_legal, cpu_trace, cpu_traces, py_trace, quantised_model,
+                         rescore, two_core_batch)
+from trace_ties import (ANCHORED_RULES, RULES, anchored_cases, d_takes_m_before_d, e_takes_the_smallest_k, flat_model,
+                        prove, smallest_cases, solve)
 
 NINF = F(-np.inf)
 
@@ -48,26 +52,6 @@ def test_tiny_models_trace_rescore_and_enumeration():
 
 
 # ---- tie-breaks: hand-built models with an exact float tie, the expected trace written out by hand ----------
-
-def flat_model(leng, e=-3.0):
-    """Every match score `e`, transitions of a plain model, J out of reach (tr_E_J = -50), tr_E_C = -0.5."""
-    M = leng + 1
-    msc = np.full((20, M), F(e), F)
-    msc[:, 0] = NINF
-    tsc = np.full((M, 7), F(-2.0), F)
-    return msc, tsc, (F(-1.0), F(-0.5), F(-50.0))
-
-
-def solve(fn, target, x0):
-    """A float32 x near x0 with fn(x) == target exactly (a few ulps around x0 are tried)."""
-    lo = hi = F(x0)
-    for _ in range(64):
-        for x in (lo, hi):
-            if fn(x) == target:
-                return x
-        lo, hi = np.nextafter(lo, F(-np.inf)), np.nextafter(hi, F(np.inf))
-    raise AssertionError("no exact tie near x0")
-
 
 def test_tie_e_takes_the_smaller_node():
     # two nodes with identical columns, one residue: M(1,1) == M(1,2) == E(1)
@@ -128,6 +112,119 @@ def test_tie_c_takes_the_loop_before_e():
     assert doms == [(1, 1, 1, 1, b"M")]         # not the domain at residue 2
     assert bits(rescore(msc, None, tsc, consts, codes, doms)) == bits(sc)
     assert bits(rescore(msc, None, tsc, consts, codes, [(2, 2, 1, 1, b"M")])) == bits(sc)
+
+
+# ---- all twelve rules through trace_ties' builder, each case proven without either trace ----------------------------
+
+def e_cases(leng):
+    """E ties in a model of LENG >= 4: neighbours, the two ends, a three-way tie given in falling order."""
+    mid = leng // 2
+    return [e_takes_the_smallest_k(leng, ks) for ks in ((mid, mid + 1), (1, leng), (leng, mid, 2))]
+
+
+def proven(case):
+    return prove(case, best_path, lib_cpu)
+
+
+def assert_cpu_takes_expected(case, what):
+    sc = proven(case)
+    got_sc, doms = cpu_trace(*case.tables, case.codes)
+    assert bits(got_sc) == bits(sc), (what, got_sc, sc)
+    assert doms == case.expected, (what, doms, case.expected, case.alternatives)
+
+
+def test_every_rule_at_its_smallest_model():
+    cases = smallest_cases()
+    rules = {c.rule for c in cases}
+    assert len(rules) == ANCHORED_RULES + 1 == 12, rules
+    assert {name.split(",")[0] for name in RULES} | {"E: smallest k"} == rules
+    assert sum(c.isc is not None for c in cases) == 2 and max(c.msc.shape[1] - 1 for c in cases) == 4
+    for case in cases:
+        assert case.msc.shape[1] - 1 <= 5  # (proven against the explicit enumeration)
+        assert_cpu_takes_expected(case, case.rule)
+    # the C and the J rule on models whose exits differ; B's second domain needs J
+    by_rule = {c.rule: c for c in cases}
+    for rule in ("C: loop before E", "J: loop before E", "B: N before J"):
+        assert by_rule[rule].consts[1] != by_rule[rule].consts[2]
+    assert len(by_rule["B: N before J"].alternatives[0]) == 2 and len(by_rule["J: loop before E"].expected) == 2
+
+
+def test_every_rule_at_the_anchors_of_a_larger_model():
+    """LENG 40: the first node a rule allows, the middle, the last (LENG - 1 for the I and the D cell: no I at
+    node LENG, no D that ends at the exit).  The solved parameter is the smallest model's: it does not depend on
+    the anchor."""
+    n = 0
+    for name, k, case in anchored_cases(40, (20,)):
+        assert_cpu_takes_expected(case, (name, k))
+        if case.isc is None:  # (an insert score of the anchor's node enters the solved parameter)
+            small = RULES[name].build(max(RULES[name].first + RULES[name].tail, 1), RULES[name].first)
+            for a, b in ((case.tsc, small.tsc), (case.msc[:, 1:], small.msc[:, 1:]), (case.consts, small.consts)):
+                assert set(bits(a).ravel().tolist()) == set(bits(b).ravel().tolist()), (name, k)
+        n += 1
+    assert n == 3 * len(RULES)
+    for rule in ("I: M before I", "D: M before D"):
+        assert max(k for name, k, _ in anchored_cases(40, ()) if name == rule) == 39
+    for case in e_cases(40):
+        assert_cpu_takes_expected(case, case.rule)
+    assert_cpu_takes_expected(d_takes_m_before_d(40, 30, chain=21), "D chain")
+
+
+def builder_cases():
+    return smallest_cases() + [c for _, _, c in anchored_cases(40, (20,))] + e_cases(40)
+
+
+def assert_py_equals_cpu(tables, codes, what):
+    """py_trace against cpu_trace: score bits, domains and ops.  Returns py_trace's result."""
+    sc, doms = cpu_trace(*tables, codes)
+    t = py_trace(*tables, codes)
+    assert bits(t.score) == bits(sc), (what, t.score, sc)
+    assert t.domains == doms, (what, t.domains, doms)
+    return t
+
+
+def test_py_trace_equals_the_cpu_trace_on_tiny_models_and_builder_cases():
+    n = 0
+    for msc, isc, tsc, consts, seqs in tiny_cases():
+        for codes in seqs:
+            assert_py_equals_cpu((msc, isc, tsc, consts), codes, n)
+            n += 1
+    assert n == 5 * 2 * 6 * 7
+    for case in builder_cases():
+        t = assert_py_equals_cpu(case.tables, case.codes, case.rule)
+        assert t.domains == case.expected
+        assert t.ties[case.rule[0]] >= 1, (case.rule, t.ties)  # py_trace sees the planted tie, under its rule
+
+
+FUZZ_SEQUENCES = 1500
+
+
+def test_quantised_models_cpu_trace_equals_py_trace():
+    """Seeded models whose every score is a multiple of 0.25 or 0.5 from [-1.5, 0.75] or [-1, 0.5]: LENG 3..12,
+    L 2..10, half with distinct exits, insert scores on for a third, every other model periodic in its nodes (low
+    complexity).  The share of sequences with an on-path tie, counted by py_trace alone,
+    must be at least one in five (measured: see the assertion's message) -- else the comparison pins nothing."""
+    rng = np.random.Generator(np.random.PCG64(2024))
+    n = tied = 0
+    by_rule = dict.fromkeys("MIDECJB", 0)
+    model = 0
+    while n < FUZZ_SEQUENCES:
+        leng = int(rng.integers(3, 13))
+        tables = quantised_model(rng, leng, model % 3 == 0, model // 2 % 2 == 1, step=0.25 if model // 4 % 2 else 0.5,
+                                 depth=1.0 if model // 8 % 2 else 1.5,
+                                 period=int(rng.integers(1, leng)) if model % 2 == 0 else None)
+        model += 1
+        for _ in range(10):
+            codes = rng.integers(0, 20, int(rng.integers(2, 11)), dtype=np.uint8)
+            t = assert_py_equals_cpu(tables, codes, (model, n))
+            check_legal(t.domains, leng, len(codes))
+            assert bits(rescore(*tables, codes, t.domains)) == bits(t.score)
+            tied += t.tied
+            for rule, c in t.ties.items():
+                by_rule[rule] += c > 0
+            n += 1
+    print(f"quantised fuzz: {tied} of {n} sequences with an on-path tie; per rule {by_rule}")
+    assert 5 * tied >= n, (tied, n, by_rule)
+    assert all(by_rule[r] > 0 for r in "MIDEC"), by_rule
 
 
 # ---- bundled profiles ---------------------------------------------------------------------------------------

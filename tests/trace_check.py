@@ -96,6 +96,121 @@ def rescore(msc, isc, tsc, consts, codes, doms):
     return F(s + move)
 
 
+class PyTrace:
+    """py_trace's result: the score, the domains, per rule ("M", "I", "D", "E", "C", "J", "B") the number of
+    on-path decisions that had two or more equal candidates, and per on-path E tie the tied nodes."""
+
+    def __init__(self, score):
+        self.score, self.domains = score, []
+        self.ties = dict.fromkeys("MIDECJB", 0)
+        self.e_tied = []
+
+    @property
+    def tied(self):
+        return sum(self.ties.values()) > 0
+
+
+def py_trace(msc, isc, tsc, consts, codes):
+    """The trace by a plain float32 numpy DP that keeps the full matrices (msv.h "Viterbi traces"): the M and I
+    rows vectorised, the D chain a scalar loop.  On the way back each source is found by comparing the cell's
+    value before its emission with fl(pred + t) of every candidate, in msv.h's order; a decision with two or
+    more equal candidates is counted as a tie of its rule."""
+    tBM, tEC, tEJ = (F(x) for x in consts)
+    K, L = msc.shape[1] - 1, len(codes)
+    loop, move = (F(x) for x in msv.sequence_transitions(L))
+    Mx, Ix, Dx = (np.full((L + 1, K + 1), NINF, F) for _ in range(3))
+    N, B, J, Cc, E = (np.full(L + 1, NINF, F) for _ in range(5))
+    N[0], B[0] = F(0.0), move
+    tmm, tim, tdm, tmd, tdd = (np.ascontiguousarray(tsc[:K, c], F) for c in (MM, IM, DM, MD, DD))  # into node k from k-1
+    with np.errstate(invalid="ignore"):
+        for i in range(1, L + 1):
+            r = int(codes[i - 1])
+            bt = F(B[i - 1] + tBM)
+            m = np.maximum(np.maximum(Mx[i - 1, :K] + tmm, Ix[i - 1, :K] + tim), np.maximum(Dx[i - 1, :K] + tdm, bt))
+            Mx[i, 1:] = m + msc[r, 1:]
+            if K > 1:
+                iv = np.maximum(Mx[i - 1, 1:K] + tsc[1:K, MI], Ix[i - 1, 1:K] + tsc[1:K, II])
+                Ix[i, 1:K] = iv if isc is None else iv + isc[r, 1:K]
+            md = Mx[i, :K] + tmd  # md[k - 1] = M(i,k-1) + tMD of node k-1
+            d = NINF
+            row = Dx[i]
+            for k in range(2, K + 1):
+                d = max(md[k - 1], d + tdd[k - 1])
+                row[k] = d
+            E[i] = Mx[i, 1:].max()
+            J[i] = max(F(J[i - 1] + loop), F(E[i] + tEJ))
+            Cc[i] = max(F(Cc[i - 1] + loop), F(E[i] + tEC))
+            N[i] = F(N[i - 1] + loop)
+            B[i] = max(F(N[i] + move), F(J[i] + move))
+    out = PyTrace(F(Cc[L] + move) if L else NINF)
+    if L == 0 or not np.isfinite(out.score):
+        return out
+
+    def pick(rule, value, cands):
+        """The first candidate (name, float) equal to `value`; counts a tie when more than one is."""
+        hit = [name for name, c in cands if c == value]
+        assert hit, (rule, value, cands)
+        out.ties[rule] += len(hit) > 1
+        return hit[0]
+
+    i = L
+    while pick("C", Cc[i], [("loop", F(Cc[i - 1] + loop)), ("E", F(E[i] + tEC))]) == "loop":
+        i -= 1
+    while True:
+        nodes = np.flatnonzero(Mx[i, 1:] == E[i]) + 1
+        if len(nodes) > 1:
+            out.ties["E"] += 1
+            out.e_tied.append(nodes)
+        k = int(nodes[0])
+        i_to, k_to, ops, st = i, k, [], "M"
+        while True:
+            ops.append(st)
+            if st == "M":
+                cands = [("M", F(Mx[i - 1, k - 1] + tsc[k - 1, MM])), ("I", F(Ix[i - 1, k - 1] + tsc[k - 1, IM])),
+                         ("D", F(Dx[i - 1, k - 1] + tsc[k - 1, DM])), ("B", F(B[i - 1] + tBM))]
+                src = pick("M", max(c for _, c in cands), cands)
+                i, k = i - 1, k - 1
+                if src == "B":
+                    break
+                st = src
+            elif st == "I":
+                cands = [("M", F(Mx[i - 1, k] + tsc[k, MI])), ("I", F(Ix[i - 1, k] + tsc[k, II]))]
+                st = pick("I", max(c for _, c in cands), cands)
+                i -= 1
+            else:
+                st = pick("D", Dx[i, k], [("M", F(Mx[i, k - 1] + tsc[k - 1, MD])), ("D", F(Dx[i, k - 1] + tsc[k - 1, DD]))])
+                k -= 1
+        out.domains.append((i + 1, i_to, k + 1, k_to, "".join(reversed(ops)).encode()))
+        if i == 0 or pick("B", B[i], [("N", F(N[i] + move)), ("J", F(J[i] + move))]) == "N":
+            break
+        while pick("J", J[i], [("loop", F(J[i - 1] + loop)), ("E", F(E[i] + tEJ))]) == "loop":
+            i -= 1
+    out.domains.reverse()
+    return out
+
+
+def quantised_model(rng, leng, inserts, distinct_exits, step=0.5, emissions=None, depth=2.0, period=None):
+    """A model whose every score is a multiple of `step` from a small range, so that sums of different terms
+    coincide often: match scores from `emissions` (default: multiples of step in [-depth, depth / 2]), insert
+    scores in [-1, 0], transitions, the entry and the exits in [-depth, 0].  With `period` the nodes repeat with
+    that period (a low-complexity model): whole paths then tie with their shifted copies."""
+    M = leng + 1
+    grid = np.arange(-depth, depth / 2 + step / 2, step) if emissions is None else np.asarray(emissions, float)
+    msc = rng.choice(grid, (20, M)).astype(F)
+    msc[:, 0] = NINF
+    isc = (-step * rng.integers(0, int(1 / step) + 1, (20, M))).astype(F) if inserts else None
+    tsc = (-step * rng.integers(0, int(depth / step) + 1, (M, 7))).astype(F)
+    if period:
+        src = 1 + np.arange(leng) % period
+        msc[:, 1:], tsc[1:] = msc[:, src], tsc[src]
+        if inserts:
+            isc[:, 1:] = isc[:, src]
+    tBM = F(-step * rng.integers(1, int(depth / step) + 1))
+    tEC = F(-step * rng.integers(0, int(depth / step) + 1))
+    tEJ = F(tEC - step * rng.integers(1, 4)) if distinct_exits else tEC
+    return msc, isc, tsc, (tBM, tEC, tEJ)
+
+
 def tables_of(vit):
     """(msc, isc or None, tsc, consts) of a Viterbi_HMM, as the C calls take them."""
     return (vit.match_scores, vit.insert_scores if vit.insert_mode else None, vit.transition_scores,
