@@ -12,6 +12,7 @@ Python mirror of the reference's C++ class surface, bound to libmsv_hip.so (incl
     filter_pipeline(msv, vit, ...)          MSV -> P-value -> F1 -> Viterbi on the survivors, on the GPU
     Forward_HMM(profile)                    (new, DESIGN 4.9: the summed odds of every alignment, with P-values)
     search_pipeline(msv, vit, fwd, ...)     MSV -> F1 -> Viterbi -> F2 -> Forward -> P-value, on the GPU
+    Domain_HMM(profile)                     (new, DESIGN 4.10: Backward, domain posteriors and envelopes of each hit)
 
 Sequences use the reference's form ('#' sentinel + one-letter residues) or packed codes
 0..19 (alphabetical A C D E F G H I K L M N P Q R S T V W Y) with CSR offsets.
@@ -31,7 +32,7 @@ __all__ = [
     "AMINO_ACIDS", "MSVError", "Profile_HMM", "FASTA_protein_sequences", "MSV_HMM", "pack_sequences",
     "encode", "sequence_transitions", "device_count", "score_grid", "score_grid_device", "score_batch_multi",
     "shard_bounds", "FASTA_device", "MultiGPU", "Viterbi_HMM", "filter_pipeline", "INSERTS_ZERO",
-    "INSERTS_LOG_ODDS", "Traces", "Forward_HMM", "search_pipeline",
+    "INSERTS_LOG_ODDS", "Traces", "Forward_HMM", "search_pipeline", "Domain_HMM", "Envelopes", "dom_regions",
 ]
 
 INSERTS_ZERO = 0      # HMMER3's insert scores (background emissions: 0)
@@ -678,12 +679,135 @@ class Forward_HMM(_StageEngine):
                                                    self.forward_lambda, pvalues_ptr, stream), "msv_fwd_pvalues_device")
 
 
+class Envelopes:
+    """What Domain_HMM.decode_batch returns, per select entry q in the caller's order: forward_scores[q],
+    backward_scores[q] (nats), the per-residue posteriors begin / end / occ (float32, compacted: entry q's are
+    [residue_offsets[q], residue_offsets[q+1]), residue i at index i - 1) and the regions of the envelope rule
+    (REGION_DTYPE records seq, i_from, i_to, expected_domains, mass; entry q's are [region_offsets[q],
+    region_offsets[q+1])).  `select` are the batch indices of the entries; `status` is the call's status name."""
+
+    def __init__(self, select, forward_scores, backward_scores, residue_offsets, begin, end, occ, region_offsets,
+                 regions, status="MSV_OK", stats=None):
+        self.select = select
+        self.forward_scores, self.backward_scores = forward_scores, backward_scores
+        self.residue_offsets, self.region_offsets = residue_offsets, region_offsets
+        self.begin, self.end, self.occ = begin, end, occ
+        self.regions = regions
+        self.status = status
+        self.stats = stats or {}
+
+    def __len__(self) -> int:
+        return len(self.forward_scores)
+
+    def posteriors(self, q: int):
+        """(begin, end, occ) of entry q, float32 [L]."""
+        lo, hi = int(self.residue_offsets[q]), int(self.residue_offsets[q + 1])
+        return self.begin[lo:hi], self.end[lo:hi], self.occ[lo:hi]
+
+    def regions_of(self, q: int) -> np.ndarray:
+        return self.regions[int(self.region_offsets[q]):int(self.region_offsets[q + 1])]
+
+
+def dom_regions(begin, end, occ, rt1: float = 0.25, rt2: float = 0.10) -> np.ndarray:
+    """The envelope rule (msv_dom_regions, THE definition) on three float32 arrays of one sequence -> REGION_DTYPE
+    records (seq = 0), by the two-call sizing protocol."""
+    b, e, o = (np.ascontiguousarray(x, np.float32) for x in (begin, end, occ))
+    if not (b.shape == e.shape == o.shape and b.ndim == 1):
+        raise ValueError("begin, end and occ disagree")
+    L = _native.lib()
+    n = C.c_uint32()
+    args = (_ptr(b), _ptr(e), _ptr(o), b.size, rt1, rt2)
+    check(L.msv_dom_regions(*args, C.byref(n), None), "msv_dom_regions")
+    out = np.zeros(n.value, _native.REGION_DTYPE)
+    if n.value:
+        check(L.msv_dom_regions(*args, C.byref(n), out.ctypes.data), "msv_dom_regions")
+    return out
+
+
+class Domain_HMM(_StageEngine):
+    """Domain stage for one profile on one GPU (msv.h "Domain stage"): Backward, the per-residue domain
+    posteriors from Forward x Backward on the special states, and HMMER3's envelope rule on them.  Tables and
+    specials are Forward_HMM's.  decode_batch runs on the gfx950 kernels (dom_kernel.hip: the recording Forward
+    launch, the Backward launch, the region launches); decode_on_sequence is the library's serial float64 CPU twin,
+    which every test compares against.  score_batch returns the recording kernel's Forward score."""
+
+    _prefix, _Info = "msv_dom", _native.DomInfo
+
+    def decode_on_sequence(self, seq=None, *, codes: np.ndarray | None = None):
+        """The float64 CPU decode (msv_dom_cpu_decode) -> (forward score, backward score, begin, end, occ), the
+        arrays float64 [L]; IndexError on a residue outside the 20."""
+        if seq is not None:
+            codes = encode(seq[1:] if seq.startswith("#") else seq)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        f, b = C.c_double(), C.c_double()
+        begin, end, occ = (np.zeros(codes.size, np.float64) for _ in range(3))
+        _check_residues(_native.lib().msv_dom_cpu_decode(*self._tables(), _ptr(codes), codes.size, C.byref(f),
+                                                         C.byref(b), _ptr(begin), _ptr(end), _ptr(occ)),
+                        "msv_dom_cpu_decode")
+        return f.value, b.value, begin, end, occ
+
+    @staticmethod
+    def workspace_bytes(residues_len: int, n: int) -> int:
+        """The workspace decode_batch_device needs for a batch of n sequences and residues_len residues."""
+        return 24 * (residues_len + n)
+
+    def decode_batch_device(self, residues_ptr: int, residues_len: int, offsets_ptr: int, n: int, fwd_scores_ptr: int,
+                            bck_scores_ptr: int, begin_ptr: int, end_ptr: int, occ_ptr: int, workspace_ptr: int,
+                            workspace_bytes: int, select_ptr: int | None = None, select_count_ptr: int | None = None,
+                            stream: int | None = None) -> None:
+        """msv_dom_decode_batch_device on raw device pointers: the recording launch and the Backward launch, async on
+        `stream`; scores at the sequence's index, posteriors (float32) at the residue's CSR index."""
+        check(_native.lib().msv_dom_decode_batch_device(
+            self._p, residues_ptr, residues_len, offsets_ptr, n, select_ptr, select_count_ptr, fwd_scores_ptr,
+            bck_scores_ptr, begin_ptr, end_ptr, occ_ptr, workspace_ptr, workspace_bytes, stream),
+            "msv_dom_decode_batch_device")
+
+    def decode_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
+                     offsets: np.ndarray | None = None, select=None, rt1: float = 0.25, rt2: float = 0.10,
+                     workspace_bytes: int = 0, strict: bool = True) -> Envelopes:
+        """Scores, posteriors and regions of the selected sequences (all when select is None), computed on the GPU
+        (msv_dom_decode_batch), per select entry in the caller's order.  workspace_bytes bounds the device memory
+        for the Forward records (0: 1 GiB); the call runs in as many chunks as that takes.  A bad residue raises
+        IndexError as score_batch does, unless strict=False: then the result is returned with `status` set."""
+        codes, offsets, n = _batch(seqs, codes, offsets)
+        sel = None if select is None else np.ascontiguousarray(select, np.uint32)
+        sel_buf = sel if sel is None or sel.size else np.zeros(1, np.uint32)  # (an empty list is not "every one")
+        L = _native.lib()
+        r = C.c_void_p()
+        st = L.msv_dom_decode_batch(self._p, _ptr(codes), offsets.ctypes.data, n,
+                                    None if sel is None else sel_buf.ctypes.data, 0 if sel is None else sel.size,
+                                    rt1, rt2, workspace_bytes, C.byref(r))
+        if not r.value:
+            check(st, "msv_dom_decode_batch")
+        try:
+            if strict:
+                _check_residues(st, "msv_dom_decode_batch")
+            m = L.msv_dom_result_count(r)
+            fwd, bck = np.zeros(m, np.float32), np.zeros(m, np.float32)
+            res_off, reg_off = np.zeros(m + 1, np.uint64), np.zeros(m + 1, np.uint64)
+            begin, end, occ = (np.zeros(L.msv_dom_result_residues(r), np.float32) for _ in range(3))
+            regions = np.zeros(L.msv_dom_result_regions(r), _native.REGION_DTYPE)
+            check(L.msv_dom_result_copy(r, fwd.ctypes.data, bck.ctypes.data, res_off.ctypes.data, _ptr(begin),
+                                        _ptr(end), _ptr(occ), reg_off.ctypes.data, _ptr(regions)),
+                  "msv_dom_result_copy")
+            stats = _native.DomStats()
+            check(L.msv_dom_result_stats(r, C.byref(stats)))
+        finally:
+            L.msv_dom_result_free(r)
+        return Envelopes(np.arange(n, dtype=np.uint32) if sel is None else sel, fwd, bck, res_off, begin, end, occ,
+                         reg_off, regions, status=_native.STATUS.get(st, str(st)),
+                         stats={f: getattr(stats, f) for f, _ in stats._fields_ if f != "reserved"})
+
+
 def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Forward_HMM,
                     seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
-                    offsets: np.ndarray | None = None, F1: float = 0.02, F2: float = 1e-3) -> dict:
+                    offsets: np.ndarray | None = None, F1: float = 0.02, F2: float = 1e-3,
+                    dom_engine: "Domain_HMM | None" = None, F3: float = 1e-5) -> dict:
     """HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV over every sequence, P <= F1, Viterbi on the
     survivors, P <= F2, Forward on those, Forward P-values.  Returns the per-stage arrays: msv_scores, passed_msv,
-    vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run)."""
+    vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run).
+    With dom_engine, also "envelopes": the Envelopes of the sequences with Forward P <= F3, in index order (a second
+    call that uploads the batch again: Domain_HMM.decode_batch with select = those indices)."""
     codes, offsets, n = _batch(seqs, codes, offsets)
     stats = np.array([msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
                       fwd_engine.forward_tau, fwd_engine.forward_lambda], np.float32)
@@ -695,8 +819,12 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
         msv_engine._p, vit_engine._p, fwd_engine._p, _ptr(codes), offsets.ctypes.data, n, stats.ctypes.data, F1, F2,
         msc.ctypes.data, p1.ctypes.data, vsc.ctypes.data, p2.ctypes.data, fsc.ctypes.data, fpv.ctypes.data,
         C.byref(n1), C.byref(n2)), "msv_fwd_filter_batch")
-    return {"msv_scores": msc, "passed_msv": p1.astype(bool), "vit_scores": vsc, "passed_vit": p2.astype(bool),
-            "fwd_scores": fsc, "fwd_pvalues": fpv}
+    out = {"msv_scores": msc, "passed_msv": p1.astype(bool), "vit_scores": vsc, "passed_vit": p2.astype(bool),
+           "fwd_scores": fsc, "fwd_pvalues": fpv}
+    if dom_engine is not None:
+        hits = np.flatnonzero(p2.astype(bool) & (fpv <= F3)).astype(np.uint32)
+        out["envelopes"] = dom_engine.decode_batch(codes=codes, offsets=offsets, select=hits)
+    return out
 
 
 def _handles(engines: Sequence[MSV_HMM]):

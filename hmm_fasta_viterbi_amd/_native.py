@@ -63,6 +63,13 @@ EXPORTED = [
     "msv_fwd_profile_reserve_length", "msv_fwd_profile_describe", "msv_fwd_variant_count", "msv_fwd_variant_name",
     "msv_fwd_profile_set_variant", "msv_fwd_score_batch_device", "msv_fwd_profile_bind_stream",
     "msv_fwd_score_batch", "msv_fwd_profile_check", "msv_fwd_pvalues_device", "msv_fwd_filter_batch",
+    "msv_dom_cpu_decode", "msv_dom_cpu_decode_batch", "msv_dom_regions", "msv_dom_scan_constants",
+    "msv_dom_sequence_bytes", "msv_dom_profile_create", "msv_dom_profile_create_from_hmm", "msv_dom_profile_destroy",
+    "msv_dom_profile_reserve_length", "msv_dom_profile_describe", "msv_dom_variant_count", "msv_dom_variant_name",
+    "msv_dom_profile_set_variant", "msv_dom_profile_bind_stream", "msv_dom_profile_check",
+    "msv_dom_score_batch_device", "msv_dom_score_batch", "msv_dom_decode_batch_device", "msv_dom_decode_batch",
+    "msv_dom_result_count", "msv_dom_result_residues", "msv_dom_result_regions", "msv_dom_result_copy",
+    "msv_dom_result_free", "msv_dom_result_stats",
 ]
 
 
@@ -147,6 +154,44 @@ class FwdInfo(C.Structure):
         d = {f: getattr(self, f) for f, _ in self._fields_}
         d["variant"] = self.variant.decode()
         return d
+
+
+class DomInfo(C.Structure):
+    """msv_dom_info: append-only, struct_size first (set before the call)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("model_length", C.c_uint32),
+        ("states_per_lane", C.c_uint32),
+        ("match_in_lds", C.c_uint32),
+        ("insert_scores", C.c_uint32),
+        ("waves_per_block", C.c_uint32),
+        ("blocks", C.c_uint32),
+        ("backward_blocks", C.c_uint32),
+        ("lds_bytes", C.c_uint32),
+        ("backward_lds_bytes", C.c_uint32),
+        ("scratch_bytes", C.c_uint32),
+        ("max_length", C.c_uint32),
+        ("device", C.c_int),
+        ("variant", C.c_char * 64),
+    ]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(DomInfo)
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "struct_size"}
+        d["variant"] = self.variant.decode()
+        return d
+
+
+class DomStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint64), ("record_bytes", C.c_uint64), ("forward_ms", C.c_float),
+                ("backward_ms", C.c_float), ("regions_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+# msv_dom_region as a numpy structured dtype
+REGION_DTYPE = [("seq", "<u4"), ("i_from", "<u4"), ("i_to", "<u4"), ("expected_domains", "<f4"), ("mass", "<f4")]
 
 
 class VitDomain(C.Structure):
@@ -328,6 +373,32 @@ def lib() -> C.CDLL:
         "msv_fwd_pvalues_device": (C.c_int, [C.c_int, vp, vp, u64, f32, f32, vp, vp]),
         "msv_fwd_filter_batch": (C.c_int, [vp, vp, vp, vp, vp, u64, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp,
                                            vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "msv_dom_cpu_decode": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, u64, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), vp, vp, vp]),
+        "msv_dom_cpu_decode_batch": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "msv_dom_regions": (C.c_int, [vp, vp, vp, u64, f32, f32, C.POINTER(u32), vp]),
+        "msv_dom_scan_constants": (C.c_int, [vp, u32, u32, vp, vp, vp]),
+        "msv_dom_sequence_bytes": (u64, [u64]),
+        "msv_dom_profile_create": (C.c_int, [C.c_int, vp, vp, vp, u32, f32, f32, f32, C.POINTER(vp)]),
+        "msv_dom_profile_create_from_hmm": (C.c_int, [C.c_int, vp, C.c_int, C.POINTER(vp)]),
+        "msv_dom_profile_destroy": (None, [vp]),
+        "msv_dom_profile_reserve_length": (C.c_int, [vp, u64]),
+        "msv_dom_profile_describe": (C.c_int, [vp, C.POINTER(DomInfo)]),
+        "msv_dom_variant_count": (C.c_int, []),
+        "msv_dom_variant_name": (C.c_char_p, [C.c_int]),
+        "msv_dom_profile_set_variant": (C.c_int, [vp, C.c_char_p]),
+        "msv_dom_profile_bind_stream": (C.c_int, [vp, vp]),
+        "msv_dom_profile_check": (C.c_int, [vp, vp]),
+        "msv_dom_score_batch_device": (C.c_int, [vp, vp, u64, vp, u64, vp, vp, vp, vp]),
+        "msv_dom_score_batch": (C.c_int, [vp, vp, vp, u64, vp, vp]),
+        "msv_dom_decode_batch_device": (C.c_int, [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "msv_dom_decode_batch": (C.c_int, [vp, vp, vp, u64, vp, u64, f32, f32, u64, C.POINTER(vp)]),
+        "msv_dom_result_count": (u64, [vp]),
+        "msv_dom_result_residues": (u64, [vp]),
+        "msv_dom_result_regions": (u64, [vp]),
+        "msv_dom_result_copy": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "msv_dom_result_free": (None, [vp]),
+        "msv_dom_result_stats": (C.c_int, [vp, C.POINTER(DomStats)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

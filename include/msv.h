@@ -532,7 +532,8 @@ msv_status msv_vit_traces_stats(const msv_vit_traces* traces, msv_vit_trace_stat
  * may differ within the tolerance.
  * P-value (HMMER3): bits = (score - nullsc) / ln 2 with msv_pvalues' null1 nullsc; P = 1 when bits < tau,
  * else exp(-lambda (bits - tau)); tau, lambda = STATS LOCAL FORWARD (msv_hmm_stats slots 4 and 5).  The
- * null2 / bias corrections, Backward, posterior decoding and domain envelopes are not part of this stage. */
+ * null2 / bias corrections are not part of this stage; Backward, posterior decoding and domain envelopes are
+ * the domain stage's (below). */
 typedef struct msv_fwd_profile msv_fwd_profile;
 
 /* The serial float64 CPU Forward of one sequence, arguments as msv_vit_cpu_score.  L = 0 scores -inf; a code
@@ -609,6 +610,167 @@ msv_status msv_fwd_filter_batch(msv_profile* msv, msv_vit_profile* vit, msv_fwd_
                                 float* msv_scores, uint8_t* passed_msv, float* vit_scores, uint8_t* passed_vit,
                                 float* fwd_scores, double* fwd_pvalues, uint64_t* n_passed_msv,
                                 uint64_t* n_passed_vit);
+
+/* ---- Domain stage: Backward, domain posteriors and envelopes of each hit ------------
+ * Where a hit's domains are and how many, judged by probability mass over EVERY alignment (the Viterbi
+ * trace gives the single best path).  Forward values f are exactly those of the Forward block above.
+ * Backward values b are odds: b_X(i) is the summed odds of every completion of a path that is in state X
+ * having emitted residues 1..i.  With r = residue i+1, L the length, transitions out of node k for
+ * k = 1..LENG-1 (0 elsewhere) and no I at node LENG:
+ *   row L:  bC(L) = move;  bE(L) = tEC bC(L);  bJ(L) = bN(L) = bB(L) = 0;  bI(L,k) = 0;  and the silent
+ *           chain still runs, k = LENG..1:
+ *             bD(L,k) = [k>=2] bE(L) + tDD[k] bD(L,k+1);   bM(L,k) = bE(L) + tMD[k] bD(L,k+1)
+ *   row i < L, in this order:
+ *           bB(i) = tBM sum_k m[r][k] bM(i+1,k)
+ *           bJ(i) = loop bJ(i+1) + move bB(i);  bC(i) = loop bC(i+1);  bN(i) = loop bN(i+1) + move bB(i)
+ *           bE(i) = tEJ bJ(i) + tEC bC(i)
+ *           i >= 1, k = LENG..1, g(k) = m[r][k+1] bM(i+1,k+1), h(k) = ins[r][k] bI(i+1,k):
+ *             bD(i,k) = [k>=2] bE(i) + tDM[k] g(k) + tDD[k] bD(i,k+1)
+ *             bM(i,k) = bE(i) + tMM[k] g(k) + tMI[k] h(k) + tMD[k] bD(i,k+1)
+ *             bI(i,k) = tIM[k] g(k) + tII[k] h(k)
+ * The Backward score is log bN(0); it equals the Forward score up to rounding.  With Z = fC(L) move the
+ * per-residue outputs are, for i = 1..L (stored at index i-1 of the sequence's residues):
+ *   begin[i] = fB(i-1) bB(i-1) / Z      a domain's first match state emits residue i
+ *   end[i]   = fE(i) bE(i) / Z          a domain's last emitted residue is i
+ *   occ[i]   = 1 - loop (fN(i-1) bN(i) + fJ(i-1) bJ(i) + fC(i-1) bC(i)) / Z     residue i lies in a domain
+ * Envelope rule (HMMER3's posterior heuristic; rt1 = 0.25, rt2 = 0.10 are its defaults): scan j = 1..L
+ * with `start` unset and `triggered` false.  While not triggered: if occ[j] - begin[j] < rt2, start = j;
+ * else if start is unset, start = j; then, if occ[j] >= rt1, triggered.  While triggered: if
+ * occ[j] - end[j] < rt2, the region (start, j) is emitted, start unset, triggered cleared.  A region open
+ * at L is not emitted.  Each region carries two serial float sums over its residues in index order:
+ * expected_domains = sum begin, mass = sum occ.  Resolving a region with expected_domains well above 1
+ * into single domains (stochastic clustering, null2, per-envelope rescoring) is not part of this stage.
+ * The CPU function runs all this serially in float64 (odds rescaled by 2^256, as msv_fwd_cpu_score) and is
+ * the reference of every test.  The device computes float32 odds rescaled by exact powers of two, Forward
+ * and Backward each with its own running exponent; the exponents combine exactly, and for every residue
+ *   |gpu - cpu64| <= 48 (L + LENG) 2^-24 + 8 2^-24     absolute, for begin, end and occ
+ * (every term is non-negative, each of the three factors f, b, 1/Z carries Forward's relative bound
+ * 16 (L + LENG) 2^-24 -- a Backward state step makes no more rounded operations than a Forward one, its
+ * scan is as deep -- and every posterior is <= 1; DESIGN 4.10 derives it).  Forward's own bound holds for
+ * the Backward score.  The recording Forward kernel returns the Forward kernel's score of the same
+ * variant bit for bit.  Device results are deterministic as the Forward stage's are. */
+typedef struct msv_dom_profile msv_dom_profile;
+typedef struct msv_dom_result msv_dom_result;
+
+typedef struct msv_dom_region {
+    uint32_t seq;                  /* index of the sequence in the batch                            */
+    uint32_t i_from, i_to;         /* 1-based first and last residue of the region                  */
+    float expected_domains;        /* sum of begin over the region                                  */
+    float mass;                    /* sum of occ over the region                                    */
+} msv_dom_region;
+
+/* The serial float64 CPU decode of one sequence, model arguments as msv_fwd_cpu_score: both scores (nats) and
+ * begin / end / occ as double [L]; any output may be NULL.  L = 0 gives -inf scores and writes no per-residue
+ * output; a code >= 20 gives MSV_ERR_BAD_RESIDUE.  The batch form decodes a CSR batch on a few host threads;
+ * its per-residue outputs are indexed by residue from the batch's first (offsets[s] - offsets[0]). */
+msv_status msv_dom_cpu_decode(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                              uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                              uint64_t L, double* fwd_score, double* bck_score, double* begin, double* end,
+                              double* occ);
+msv_status msv_dom_cpu_decode_batch(const float* match_scores, const float* insert_scores,
+                                    const float* transition_scores, uint32_t model_length, float tr_B_Mk, float tr_E_C,
+                                    float tr_E_J, const uint8_t* codes, const uint64_t* offsets, uint64_t n,
+                                    double* fwd_scores, double* bck_scores, double* begin, double* end, double* occ);
+/* The envelope rule above on the three float arrays of one sequence: THE definition of the rule, which the
+ * device kernels reproduce bit for bit on the same arrays.  Two calls size the output as msv_vit_cpu_trace:
+ * with regions NULL only *n_regions is written; then regions[*n_regions] (seq = 0). */
+msv_status msv_dom_regions(const float* begin, const float* end, const float* occ, uint64_t L, float rt1, float rt2,
+                           uint32_t* n_regions, msv_dom_region* regions);
+/* The Backward D-scan constants of a variant of states_per_lane = S (host-only, what the device layer uploads;
+ * the mirror of msv_fwd_scan_constants): per lane l and slot q (state k = l S + q + 1), slot_dd[l S + q] = the
+ * float32 odds of the d->d transition OUT of node k (0 where none), slot_suffix[l S + q] = the product of the
+ * lane's slot_dd q..S-1, step_products[j * 64 + l] = the product of the whole-lane products of lanes
+ * l .. min(63, l + 2^j - 1) (j = 0..5), computed in float64 from the float32 odds.  Any output may be NULL. */
+msv_status msv_dom_scan_constants(const float* transition_scores, uint32_t model_length, uint32_t states_per_lane,
+                                  float* slot_dd, float* slot_suffix, float* step_products);
+/* Workspace bytes of one selected sequence of L residues: L + 1 rows (row 0 included) of six 32-bit words, the
+ * recording kernel's N, J, C, B, E and running exponent.  Chunks are cut by msv_vit_trace_chunk_cuts. */
+uint64_t msv_dom_sequence_bytes(uint64_t L);
+
+/* Device-resident domain profile; arguments, threading, streams and variants (S = 2, 6, 12, 22, 38, with and
+ * without insert odds, LENG <= 2432) as msv_fwd_profile_create. */
+msv_status msv_dom_profile_create(int device, const float* match_scores, const float* insert_scores,
+                                  const float* transition_scores, uint32_t model_length, float tr_B_Mk, float tr_E_C,
+                                  float tr_E_J, msv_dom_profile** out);
+msv_status msv_dom_profile_create_from_hmm(int device, const msv_hmm* hmm, int insert_mode, msv_dom_profile** out);
+void msv_dom_profile_destroy(msv_dom_profile* profile);
+msv_status msv_dom_profile_reserve_length(msv_dom_profile* profile, uint64_t max_length);
+
+/* Append-only: struct_size is set by the caller to sizeof(msv_dom_info) before the call; the library writes no
+ * more than that many bytes, so a caller built against an older header keeps working when fields are added. */
+typedef struct msv_dom_info {
+    uint32_t struct_size;
+    uint32_t model_length;    /* LENG + 1                                                   */
+    uint32_t states_per_lane; /* S: one sequence per 64-lane wave, 64 * S >= LENG             */
+    uint32_t match_in_lds;    /* match odds staged in LDS (else read from L2 every row)      */
+    uint32_t insert_scores;   /* informative insert odds (read from L2)                      */
+    uint32_t waves_per_block;
+    uint32_t blocks;          /* persistent grid of a full recording launch                 */
+    uint32_t backward_blocks; /* persistent grid of a full Backward launch                  */
+    uint32_t lds_bytes;       /* of the recording kernel                                    */
+    uint32_t backward_lds_bytes;
+    uint32_t scratch_bytes;   /* private memory per lane, the larger of the two kernels' (0: no spills) */
+    uint32_t max_length;
+    int device;
+    char variant[64];
+} msv_dom_info;
+msv_status msv_dom_profile_describe(const msv_dom_profile* profile, msv_dom_info* out);
+int msv_dom_variant_count(void);
+const char* msv_dom_variant_name(int i);
+msv_status msv_dom_profile_set_variant(msv_dom_profile* profile, const char* name);
+msv_status msv_dom_profile_bind_stream(msv_dom_profile* profile, void* stream);
+msv_status msv_dom_profile_check(msv_dom_profile* profile, void* stream);
+
+/* The recording kernel's Forward score (nothing recorded): arguments and error classes as msv_fwd_score_batch
+ * [_device]; the bits are the Forward kernel's of the same S and insert mode. */
+msv_status msv_dom_score_batch_device(msv_dom_profile* profile, const uint8_t* d_residues, uint64_t residues_len,
+                                      const uint64_t* d_offsets, uint64_t n, const uint32_t* d_select,
+                                      const uint32_t* d_select_count, float* d_scores, void* stream);
+msv_status msv_dom_score_batch(msv_dom_profile* profile, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                               float* scores, void* stream);
+
+/* Decode on device buffers, asynchronous on `stream`: two launches (the recording Forward, then Backward) over
+ * the sequences of d_select / d_select_count (as msv_fwd_score_batch_device).  Written at the sequence's index:
+ * d_fwd_scores, d_bck_scores; at the residue's CSR index (offsets are absolute into these arrays, which hold
+ * residues_len floats): d_begin, d_end, d_occ.  d_workspace holds workspace_bytes >= 24 (residues_len + n)
+ * bytes (sequence s records its rows from row offsets[s] + s), else MSV_ERR_OUT_OF_MEMORY.  Error classes are
+ * Forward's: an empty sequence scores -inf, a bad residue +inf (latched), a too-long sequence NaN (latched), a
+ * select entry >= n is skipped (latched); in every error case the sequence's per-residue outputs are untouched. */
+msv_status msv_dom_decode_batch_device(msv_dom_profile* profile, const uint8_t* d_residues, uint64_t residues_len,
+                                       const uint64_t* d_offsets, uint64_t n, const uint32_t* d_select,
+                                       const uint32_t* d_select_count, float* d_fwd_scores, float* d_bck_scores,
+                                       float* d_begin, float* d_end, float* d_occ, void* d_workspace,
+                                       uint64_t workspace_bytes, void* stream);
+
+/* Decode and envelopes of the selected sequences of a host batch, synchronous.  select NULL = every sequence
+ * (n_select ignored); an entry >= n gives MSV_ERR_INVALID_ARGUMENT.  Results are per select entry, in the
+ * caller's order (an index may repeat).  workspace_bytes bounds the device memory for the Forward records (0 =
+ * the default, 1 GiB): the selected sequences run in chunks that fit it, and a sequence that alone exceeds it
+ * gives MSV_ERR_OUT_OF_MEMORY before anything is launched.  The envelope rule runs on the device (one count
+ * launch, an exclusive scan, one place launch).  MSV_ERR_BAD_RESIDUE / MSV_ERR_SEQUENCE_TOO_LONG are reported
+ * as msv_fwd_score_batch reports them and *result is still returned: the offending entries have their scores'
+ * error class, zero posteriors and no regions; the others are decoded. */
+msv_status msv_dom_decode_batch(msv_dom_profile* profile, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                                const uint32_t* select, uint64_t n_select, float rt1, float rt2,
+                                uint64_t workspace_bytes, msv_dom_result** result);
+uint64_t msv_dom_result_count(const msv_dom_result* result);      /* select entries */
+uint64_t msv_dom_result_residues(const msv_dom_result* result);   /* residues of all entries */
+uint64_t msv_dom_result_regions(const msv_dom_result* result);    /* regions in all */
+/* fwd_scores[count], bck_scores[count], residue_offsets[count + 1] (entry q's posteriors are [q], [q+1]),
+ * begin[], end[], occ[] (compacted, entry after entry), region_offsets[count + 1], regions[]; any may be NULL. */
+msv_status msv_dom_result_copy(const msv_dom_result* result, float* fwd_scores, float* bck_scores,
+                               uint64_t* residue_offsets, float* begin, float* end, float* occ,
+                               uint64_t* region_offsets, msv_dom_region* regions);
+void msv_dom_result_free(msv_dom_result* result);
+/* What the call did on the device: its chunks, the record bytes written, and the summed device times of the
+ * recording launches, the Backward launches and the three region launches (HIP events). */
+typedef struct msv_dom_stats {
+    uint64_t chunks;
+    uint64_t record_bytes;
+    float forward_ms, backward_ms, regions_ms;
+    uint32_t reserved;
+} msv_dom_stats;
+msv_status msv_dom_result_stats(const msv_dom_result* result, msv_dom_stats* out);
 
 #ifdef __cplusplus
 } /* extern "C" */

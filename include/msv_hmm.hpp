@@ -252,3 +252,40 @@ struct Search_result {
 };
 Search_result search_pipeline(MSV_HMM& msv, Viterbi_HMM& vit, Forward_HMM& fwd, const Packed_sequences& packed,
                               const Profile_HMM& stats, double F1 = 0.02, double F2 = 1e-3);
+
+// The domain stage (msv.h "Domain stage"): Backward, the per-residue domain posteriors and the
+// envelopes of each selected sequence, on the GPU (decode_batch) or by the float64 CPU twin (decode_on_sequence).
+// Per select entry q: scores [q], posteriors [residue_offsets[q], residue_offsets[q+1]), regions
+// [region_offsets[q], region_offsets[q+1]).
+struct Envelopes {
+    std::vector<Log_score> forward_scores, backward_scores;
+    std::vector<uint64_t> residue_offsets, region_offsets;
+    std::vector<float> begin, end, occ;
+    std::vector<msv_dom_region> regions;
+};
+struct Decoded_sequence {
+    double forward_score = 0, backward_score = 0;
+    std::vector<double> begin, end, occ;
+};
+class Domain_HMM {
+  public:
+    explicit Domain_HMM(const Profile_HMM& base_hmm, int device = 0, msv_insert_mode inserts = MSV_INSERTS_ZERO);
+    ~Domain_HMM();
+    Domain_HMM(const Domain_HMM&) = delete;
+    Domain_HMM& operator=(const Domain_HMM&) = delete;
+
+    Decoded_sequence decode_on_sequence(const Protein_sequence& seq);
+    // select empty = every sequence; workspace_bytes 0 = the default (1 GiB)
+    Envelopes decode_batch(const Packed_sequences& packed, const std::vector<uint32_t>& select = {},
+                           float rt1 = 0.25f, float rt2 = 0.10f, uint64_t workspace_bytes = 0);
+
+    msv_dom_profile* handle() { return profile_; }
+    size_t model_length() const { return model_length_; }
+
+  private:
+    size_t model_length_ = 0;
+    bool inserts_ = false;
+    std::vector<float> match_scores_, insert_scores_, transition_scores_;  // [20][M], [20][M], [M][7]
+    float tr_B_Mk_ = 0, tr_E_C_ = 0, tr_E_J_ = 0;
+    msv_dom_profile* profile_ = nullptr;
+};
