@@ -12,7 +12,9 @@ Python mirror of the reference's C++ class surface, bound to libmsv_hip.so (incl
     filter_pipeline(msv, vit, ...)          MSV -> P-value -> F1 -> Viterbi on the survivors, on the GPU
     Forward_HMM(profile)                    (new, DESIGN 4.9: the summed odds of every alignment, with P-values)
     search_pipeline(msv, vit, fwd, ...)     MSV -> F1 -> Viterbi -> F2 -> Forward -> P-value, on the GPU
-    Domain_HMM(profile)                     (new, DESIGN 4.10: Backward, domain posteriors and envelopes of each hit)
+    Domain_HMM(profile)                     (new, DESIGN 4.10: Backward, domain posteriors and envelopes of each hit;
+                                             DESIGN 4.11: align_batch, the posterior decoding and optimal-accuracy
+                                             alignment of each envelope)
 
 Sequences use the reference's form ('#' sentinel + one-letter residues) or packed codes
 0..19 (alphabetical A C D E F G H I K L M N P Q R S T V W Y) with CSR offsets.
@@ -33,6 +35,7 @@ __all__ = [
     "encode", "sequence_transitions", "device_count", "score_grid", "score_grid_device", "score_batch_multi",
     "shard_bounds", "FASTA_device", "MultiGPU", "Viterbi_HMM", "filter_pipeline", "INSERTS_ZERO",
     "INSERTS_LOG_ODDS", "Traces", "Forward_HMM", "search_pipeline", "Domain_HMM", "Envelopes", "dom_regions",
+    "Alignments", "aln_oa",
 ]
 
 INSERTS_ZERO = 0      # HMMER3's insert scores (background emissions: 0)
@@ -724,6 +727,83 @@ def dom_regions(begin, end, occ, rt1: float = 0.25, rt2: float = 0.10) -> np.nda
     return out
 
 
+class Alignments:
+    """What Domain_HMM.align_batch returns, per item q in the caller's order (msv.h "Alignment stage"): `items`
+    (ITEM_DTYPE records seq, i_from, i_to), envelope_scores[q] = log Z of the envelope (nats), domain_scores[q] =
+    HMMER's per-domain score, the envelope score plus (Lc - Le) log(loop) for the flanks, oa_scores[q] = the expected
+    number of correctly labelled residues of the optimal-accuracy path and accuracy[q] = oa / Le; the path as the
+    Viterbi trace reports one (`domains`, DOMAIN_DTYPE records with the parent's seq and residues relative to the
+    parent, entry q's are domains[domain_offsets[q]:domain_offsets[q+1]]; `ops`, one byte 'M' / 'I' / 'D' per core
+    state visited) and `op_pp`, one float32 per op: the posterior of the op's cell (0 for 'D').  `status` is the
+    call's status name, `stats` what the device did."""
+
+    def __init__(self, items, envelope_scores, domain_scores, oa_scores, domain_offsets, domains, ops, op_pp, *,
+                 status="MSV_OK", stats=None, posteriors=None):
+        self.items = items
+        self.envelope_scores, self.domain_scores, self.oa_scores = envelope_scores, domain_scores, oa_scores
+        Le = (items["i_to"].astype(np.int64) - items["i_from"].astype(np.int64) + 1).astype(np.float32)
+        self.accuracy = (oa_scores / np.maximum(Le, 1)).astype(np.float32)
+        self.domain_offsets, self.domains, self.ops, self.op_pp = domain_offsets, domains, ops, op_pp
+        self.status = status
+        self.stats = stats or {}
+        self._posteriors = posteriors
+
+    def __len__(self) -> int:
+        return len(self.envelope_scores)
+
+    def domains_of(self, q: int) -> np.ndarray:
+        return self.domains[int(self.domain_offsets[q]):int(self.domain_offsets[q + 1])]
+
+    def ops_of(self, d) -> bytes:
+        return self.ops[int(d["ops_begin"]):int(d["ops_begin"]) + int(d["ops_len"])].tobytes()
+
+    def pp_of(self, d) -> np.ndarray:
+        return self.op_pp[int(d["ops_begin"]):int(d["ops_begin"]) + int(d["ops_len"])]
+
+    def pp_line(self, d) -> str:
+        """HMMER's PP line of a domain, one character per op: '*' if p + 0.05 >= 1, else the digit int(10 p + 0.5);
+        '.' opposite a delete, which emits no residue."""
+        out = []
+        for op, p in zip(self.ops_of(d), self.pp_of(d)):
+            out.append("." if op == 68 else "*" if float(p) + 0.05 >= 1.0 else str(int(10.0 * float(p) + 0.5)))
+        return "".join(out)
+
+    def posteriors(self, q: int):
+        """(ppM, ppI, ppN, ppJ, ppC) of item q as the device computed them (keep_posteriors=True): ppM, ppI float32
+        [Le, LENG + 1] (row i - 1, column k), the others float32 [Le]."""
+        if self._posteriors is None:
+            raise ValueError("these alignments were made without keep_posteriors")
+        return self._posteriors[q]
+
+
+def aln_oa(ppM, ppI, ppN, ppJ, ppC, transition_scores, consts, Lc: int | None = None):
+    """THE definition of the optimal-accuracy alignment (msv_aln_oa) on float32 posteriors of one envelope: ppM, ppI
+    [Le, LENG + 1], ppN, ppJ, ppC [Le]; consts = (tr_B_Mk, tr_E_C, tr_E_J); Lc the configured length (default Le).
+    Returns (oa score, domains, ops, op_pp) by the two-call sizing protocol, i relative to the envelope."""
+    pm, pi, pn, pj, pc = (np.ascontiguousarray(x, np.float32) for x in (ppM, ppI, ppN, ppJ, ppC))
+    tsc = np.ascontiguousarray(transition_scores, np.float32)
+    Le, M = pn.size, tsc.shape[0]
+    if not (pm.shape == pi.shape == (Le, M) and pj.shape == pc.shape == (Le,) and tsc.shape == (M, 7)):
+        raise ValueError("posterior arrays and transition scores disagree")
+    L = _native.lib()
+    sc, nd, no = C.c_float(), C.c_uint32(), C.c_uint64()
+    args = (_ptr(pm), _ptr(pi), _ptr(pn), _ptr(pj), _ptr(pc), tsc.ctypes.data, M, *[float(x) for x in consts], Le,
+            Le if Lc is None else Lc)
+    check(L.msv_aln_oa(*args, C.byref(sc), C.byref(nd), C.byref(no), None, None, None), "msv_aln_oa")
+    doms = np.zeros(nd.value, _native.DOMAIN_DTYPE)
+    ops, pp = np.zeros(no.value, np.uint8), np.zeros(no.value, np.float32)
+    if nd.value:
+        check(L.msv_aln_oa(*args, C.byref(sc), C.byref(nd), C.byref(no), doms.ctypes.data, ops.ctypes.data,
+                           pp.ctypes.data), "msv_aln_oa")
+    return np.float32(sc.value), doms, ops, pp
+
+
+def _domain_scores(envelope_scores, Le, Lc) -> np.ndarray:
+    """envelope score + (Lc - Le) log(loop of Lc): HMMER's per-domain score, float32 adds on float32 values."""
+    loops = np.array([sequence_transitions(int(x))[0] for x in Lc], np.float32)
+    return (envelope_scores + (np.asarray(Lc, np.float32) - np.asarray(Le, np.float32)) * loops).astype(np.float32)
+
+
 class Domain_HMM(_StageEngine):
     """Domain stage for one profile on one GPU (msv.h "Domain stage"): Backward, the per-residue domain
     posteriors from Forward x Backward on the special states, and HMMER3's envelope rule on them.  Tables and
@@ -798,16 +878,126 @@ class Domain_HMM(_StageEngine):
                          reg_off, regions, status=_native.STATUS.get(st, str(st)),
                          stats={f: getattr(stats, f) for f, _ in stats._fields_ if f != "reserved"})
 
+    def align_describe(self) -> dict:
+        """msv_aln_describe: the alignment stage's variant, grids and, per kernel, scratch and LDS bytes."""
+        info = _native.AlnInfo()
+        check(_native.lib().msv_aln_describe(self._p, C.byref(info)), "msv_aln_describe")
+        return info.as_dict()
+
+    def align_on_sequence(self, seq=None, *, codes: np.ndarray | None = None, Lc: int | None = None):
+        """The CPU twin of the alignment stage for one envelope given as a sequence of its own (msv_aln_cpu_align):
+        the float64 decode rounded to float32, then the definition.  Lc is the configured length (default: the
+        envelope's).  Returns (envelope score float64, oa score float32, domains, ops, op_pp)."""
+        if seq is not None:
+            codes = encode(seq[1:] if seq.startswith("#") else seq)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        L = _native.lib()
+        sc, oa, nd, no = C.c_double(), C.c_float(), C.c_uint32(), C.c_uint64()
+        args = (*self._tables(), _ptr(codes), codes.size, codes.size if Lc is None else Lc)
+        _check_residues(L.msv_aln_cpu_align(*args, C.byref(sc), C.byref(oa), C.byref(nd), C.byref(no), None, None,
+                                            None), "msv_aln_cpu_align")
+        doms = np.zeros(nd.value, _native.DOMAIN_DTYPE)
+        ops, pp = np.zeros(no.value, np.uint8), np.zeros(no.value, np.float32)
+        if nd.value:
+            check(L.msv_aln_cpu_align(*args, C.byref(sc), C.byref(oa), C.byref(nd), C.byref(no), doms.ctypes.data,
+                                      ops.ctypes.data, pp.ctypes.data), "msv_aln_cpu_align")
+        return sc.value, np.float32(oa.value), doms, ops, pp
+
+    def posteriors_on_sequence(self, seq=None, *, codes: np.ndarray | None = None, Lc: int | None = None):
+        """The float64 CPU decode of one envelope (msv_aln_cpu_decode) -> (score, ppM, ppI, ppN, ppJ, ppC), ppM and
+        ppI float64 [Le, LENG + 1]."""
+        if seq is not None:
+            codes = encode(seq[1:] if seq.startswith("#") else seq)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        Le, M = codes.size, self.model_length
+        sc = C.c_double()
+        pm, pi = np.zeros((Le, M), np.float64), np.zeros((Le, M), np.float64)
+        pn, pj, pc = (np.zeros(Le, np.float64) for _ in range(3))
+        _check_residues(_native.lib().msv_aln_cpu_decode(*self._tables(), _ptr(codes), Le, Le if Lc is None else Lc,
+                                                         C.byref(sc), _ptr(pm), _ptr(pi), _ptr(pn), _ptr(pj),
+                                                         _ptr(pc)), "msv_aln_cpu_decode")
+        return sc.value, pm, pi, pn, pj, pc
+
+    def align_batch(self, seqs: Sequence[str] | None = None, items=None, *, codes: np.ndarray | None = None,
+                    offsets: np.ndarray | None = None, envelopes: "Envelopes | None" = None,
+                    workspace_bytes: int = 0, keep_posteriors: bool = False, strict: bool = True) -> Alignments:
+        """Posterior decoding and the optimal-accuracy alignment of envelopes, on the GPU (msv_aln_align_batch).
+        `items` are (seq, i_from, i_to) triples (1-based, inclusive) or ITEM_DTYPE records; envelopes= takes an
+        Envelopes and aligns every region of it.  Each item is decoded as a sequence of its own whose loop / move are
+        those of the parent's length.  workspace_bytes bounds the device workspace (0: 1 GiB); keep_posteriors keeps
+        the device's posteriors on the host (8 Le (LENG + 1) bytes an item).  A bad residue inside an item raises
+        IndexError unless strict=False: then that item has no domains and `status` says so."""
+        codes, offsets, n = _batch(seqs, codes, offsets)
+        if envelopes is not None:
+            if items is not None:
+                raise ValueError("give items or envelopes, not both")
+            reg = envelopes.regions
+            it = np.zeros(len(reg), _native.ITEM_DTYPE)
+            it["seq"], it["i_from"], it["i_to"] = reg["seq"], reg["i_from"], reg["i_to"]
+        elif items is None:
+            raise ValueError("align_batch needs items or envelopes")
+        else:
+            src = np.asarray(items)
+            if src.dtype.names:
+                it = np.zeros(len(src), _native.ITEM_DTYPE)
+                for f in ("seq", "i_from", "i_to"):
+                    it[f] = src[f]
+            else:
+                src = src.reshape(-1, 3)
+                if src.size and (src.min() < 0 or src.max() >= 2 ** 32):
+                    raise ValueError("an item outside 32 bits")
+                it = np.zeros(len(src), _native.ITEM_DTYPE)
+                it["seq"], it["i_from"], it["i_to"] = src[:, 0], src[:, 1], src[:, 2]
+        it = np.ascontiguousarray(it)
+        L = _native.lib()
+        r = C.c_void_p()
+        st = L.msv_aln_align_batch(self._p, _ptr(codes), offsets.ctypes.data, n, _ptr(it), len(it), workspace_bytes,
+                                   1 if keep_posteriors else 0, C.byref(r))
+        if not r.value:
+            check(st, "msv_aln_align_batch")
+        try:
+            if st not in (_native.MSV_OK, _native.MSV_ERR_BAD_RESIDUE):
+                check(st, "msv_aln_align_batch")
+            if strict:
+                _check_residues(st, "msv_aln_align_batch")
+            m = L.msv_aln_result_count(r)
+            env, oa = np.zeros(m, np.float32), np.zeros(m, np.float32)
+            dom_off = np.zeros(m + 1, np.uint64)
+            doms = np.zeros(L.msv_aln_result_domains(r), _native.DOMAIN_DTYPE)
+            ops = np.zeros(L.msv_aln_result_ops(r), np.uint8)
+            pp = np.zeros(len(ops), np.float32)
+            check(L.msv_aln_result_copy(r, env.ctypes.data, oa.ctypes.data, dom_off.ctypes.data, _ptr(doms), _ptr(ops),
+                                        _ptr(pp)), "msv_aln_result_copy")
+            Le = it["i_to"].astype(np.int64) - it["i_from"].astype(np.int64) + 1
+            post = None
+            if keep_posteriors:
+                post = []
+                for q in range(m):
+                    pm, pi = (np.zeros((int(Le[q]), self.model_length), np.float32) for _ in range(2))
+                    pn, pj, pc = (np.zeros(int(Le[q]), np.float32) for _ in range(3))
+                    check(L.msv_aln_result_posteriors(r, q, _ptr(pm), _ptr(pi), _ptr(pn), _ptr(pj), _ptr(pc)),
+                          "msv_aln_result_posteriors")
+                    post.append((pm, pi, pn, pj, pc))
+            stats = _native.AlnStats()
+            check(L.msv_aln_result_stats(r, C.byref(stats)))
+        finally:
+            L.msv_aln_result_free(r)
+        Lc = np.diff(offsets.astype(np.int64))[it["seq"].astype(np.int64)] if m else np.zeros(0, np.int64)
+        return Alignments(it, env, _domain_scores(env, Le, Lc), oa, dom_off, doms, ops, pp,
+                          status=_native.STATUS.get(st, str(st)),
+                          stats={f: getattr(stats, f) for f, _ in stats._fields_}, posteriors=post)
+
 
 def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Forward_HMM,
                     seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
                     offsets: np.ndarray | None = None, F1: float = 0.02, F2: float = 1e-3,
-                    dom_engine: "Domain_HMM | None" = None, F3: float = 1e-5) -> dict:
+                    dom_engine: "Domain_HMM | None" = None, F3: float = 1e-5, align: bool = False) -> dict:
     """HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV over every sequence, P <= F1, Viterbi on the
     survivors, P <= F2, Forward on those, Forward P-values.  Returns the per-stage arrays: msv_scores, passed_msv,
     vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run).
     With dom_engine, also "envelopes": the Envelopes of the sequences with Forward P <= F3, in index order (a second
-    call that uploads the batch again: Domain_HMM.decode_batch with select = those indices)."""
+    call that uploads the batch again: Domain_HMM.decode_batch with select = those indices).  With align=True (which
+    needs dom_engine) also "alignments": Domain_HMM.align_batch of every region of those envelopes."""
     codes, offsets, n = _batch(seqs, codes, offsets)
     stats = np.array([msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
                       fwd_engine.forward_tau, fwd_engine.forward_lambda], np.float32)
@@ -824,6 +1014,10 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
     if dom_engine is not None:
         hits = np.flatnonzero(p2.astype(bool) & (fpv <= F3)).astype(np.uint32)
         out["envelopes"] = dom_engine.decode_batch(codes=codes, offsets=offsets, select=hits)
+        if align:
+            out["alignments"] = dom_engine.align_batch(codes=codes, offsets=offsets, envelopes=out["envelopes"])
+    elif align:
+        raise ValueError("align=True needs dom_engine")
     return out
 
 

@@ -70,6 +70,9 @@ EXPORTED = [
     "msv_dom_score_batch_device", "msv_dom_score_batch", "msv_dom_decode_batch_device", "msv_dom_decode_batch",
     "msv_dom_result_count", "msv_dom_result_residues", "msv_dom_result_regions", "msv_dom_result_copy",
     "msv_dom_result_free", "msv_dom_result_stats",
+    "msv_aln_cpu_decode", "msv_aln_oa", "msv_aln_cpu_align", "msv_aln_item_bytes", "msv_aln_align_batch",
+    "msv_aln_result_count", "msv_aln_result_domains", "msv_aln_result_ops", "msv_aln_result_copy",
+    "msv_aln_result_posteriors", "msv_aln_result_free", "msv_aln_describe", "msv_aln_result_stats",
 ]
 
 
@@ -189,6 +192,45 @@ class DomStats(C.Structure):
     _fields_ = [("chunks", C.c_uint64), ("record_bytes", C.c_uint64), ("forward_ms", C.c_float),
                 ("backward_ms", C.c_float), ("regions_ms", C.c_float), ("reserved", C.c_uint32)]
 
+
+class AlnInfo(C.Structure):
+    """msv_aln_info: append-only, struct_size first (set before the call)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("states_per_lane", C.c_uint32),
+        ("pointer_words", C.c_uint32),
+        ("forward_blocks", C.c_uint32),
+        ("backward_blocks", C.c_uint32),
+        ("fill_blocks", C.c_uint32),
+        ("forward_scratch_bytes", C.c_uint32),
+        ("backward_scratch_bytes", C.c_uint32),
+        ("fill_scratch_bytes", C.c_uint32),
+        ("walk_scratch_bytes", C.c_uint32),
+        ("forward_lds_bytes", C.c_uint32),
+        ("backward_lds_bytes", C.c_uint32),
+        ("fill_lds_bytes", C.c_uint32),
+        ("walk_lds_bytes", C.c_uint32),
+        ("default_workspace_bytes", C.c_uint64),
+        ("variant", C.c_char * 64),
+    ]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(AlnInfo)
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "struct_size"}
+        d["variant"] = self.variant.decode()
+        return d
+
+
+class AlnStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint64), ("matrix_bytes", C.c_uint64), ("forward_ms", C.c_float),
+                ("backward_ms", C.c_float), ("fill_ms", C.c_float), ("walk_ms", C.c_float)]
+
+
+# msv_aln_item as a numpy structured dtype
+ITEM_DTYPE = [("seq", "<u4"), ("i_from", "<u4"), ("i_to", "<u4")]
 
 # msv_dom_region as a numpy structured dtype
 REGION_DTYPE = [("seq", "<u4"), ("i_from", "<u4"), ("i_to", "<u4"), ("expected_domains", "<f4"), ("mass", "<f4")]
@@ -399,6 +441,22 @@ def lib() -> C.CDLL:
         "msv_dom_result_copy": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "msv_dom_result_free": (None, [vp]),
         "msv_dom_result_stats": (C.c_int, [vp, C.POINTER(DomStats)]),
+        "msv_aln_cpu_decode": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, u64, u64, C.POINTER(C.c_double),
+                                         vp, vp, vp, vp, vp]),
+        "msv_aln_oa": (C.c_int, [vp, vp, vp, vp, vp, vp, u32, f32, f32, f32, u64, u64, C.POINTER(f32),
+                                 C.POINTER(u32), C.POINTER(u64), vp, vp, vp]),
+        "msv_aln_cpu_align": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, u64, u64, C.POINTER(C.c_double),
+                                        C.POINTER(f32), C.POINTER(u32), C.POINTER(u64), vp, vp, vp]),
+        "msv_aln_item_bytes": (u64, [u32, u64]),
+        "msv_aln_align_batch": (C.c_int, [vp, vp, vp, u64, vp, u64, u64, C.c_int, C.POINTER(vp)]),
+        "msv_aln_result_count": (u64, [vp]),
+        "msv_aln_result_domains": (u64, [vp]),
+        "msv_aln_result_ops": (u64, [vp]),
+        "msv_aln_result_copy": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "msv_aln_result_posteriors": (C.c_int, [vp, u64, vp, vp, vp, vp, vp]),
+        "msv_aln_result_free": (None, [vp]),
+        "msv_aln_describe": (C.c_int, [vp, C.POINTER(AlnInfo)]),
+        "msv_aln_result_stats": (C.c_int, [vp, C.POINTER(AlnStats)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

@@ -1,0 +1,402 @@
+// aln_device.cpp -- C-ABI of the alignment stage (msv.h) on the HIP runtime.
+//
+// The stage runs on a msv_dom_profile (dom_profile.h): the recording and the Backward kernel of aln_kernel.hip read
+// the tables the domain stage's variant installed, the fill kernel a small table of gate bytes made per call.  The
+// host packs the items' residues into a CSR batch of their own (item q is sequence q of it), cuts the items into
+// chunks that fit the workspace as the Viterbi trace's are cut, and runs five launches per chunk, each on its own
+// launch slot: recording Forward, Backward with the combine, OA fill, walk count, walk place.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "aln_host.h"
+#include "aln_kernel.h"
+#include "dom_profile.h"
+#include "hip_rt.h"
+#include "msv.h"
+#include "msv_kernel.h"
+#include "stage_profile.h"
+
+using msvrt::DeviceBuffer;
+using msvrt::DeviceGuard;
+using stagedev::kHostErrWord;
+
+struct msv_aln_result {
+    std::vector<float> env, oa;
+    std::vector<uint64_t> dom_off;
+    std::vector<msv_vit_domain> domains;
+    std::vector<uint8_t> ops;
+    std::vector<float> op_pp;
+    // keep_posteriors: per item, ppM / ppI [Le][M] and ppN / ppJ / ppC [Le]
+    bool kept = false;
+    uint32_t M = 0;
+    std::vector<std::vector<float>> pm, pi, pn, pj, pc;
+    msv_aln_stats stats{};
+};
+
+namespace {
+
+constexpr uint64_t kDefaultWorkspace = 1ull << 30;
+
+const alnk::AlnVariant* variant_of(const msv_dom_profile* p) {
+    int n = 0;
+    const alnk::AlnVariant* all = alnk::aln_variants(&n);
+    for (int i = 0; i < n; ++i)
+        if (all[i].S == p->v->S && all[i].isc == p->v->isc) return &all[i];
+    return nullptr;
+}
+
+uint32_t full_grid(int device, const void* fn, int waves) {
+    int blocks = 0;
+    (void)msvrt::resident_blocks(device, fn, waves * 64, &blocks);
+    return static_cast<uint32_t>(std::max(1, blocks));
+}
+
+// One persistent launch on the next launch slot over `items` list entries, `waves` of them a workgroup.
+msv_status run_kernel(msv_dom_profile* p, const void* fn, int waves, hipStream_t st, uint64_t items, alnk::AlnArgs& a) {
+    if (items == 0) return MSV_OK;
+    const uint64_t need = (items + static_cast<uint64_t>(waves) - 1) / static_cast<uint64_t>(waves);
+    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(full_grid(p->device, fn, waves), need));
+    MSV_HIP(p->kernels.run(st, stagedev::lazy(p, st), p->d_words.get(), 2, [&](uint32_t* counter) {
+        a.counter = counter;
+        return alnk::aln_launch(fn, waves, blocks, a, st);
+    }));
+    return MSV_OK;
+}
+
+float elapsed(const msvrt::Event& a, const msvrt::Event& b) {
+    float ms = 0.0f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;
+}
+
+template <class T>
+hipError_t upload(DeviceBuffer<T>& d, const std::vector<T>& h, hipStream_t st) {
+    hipError_t e = d.reserve(h.size());
+    if (e == hipSuccess && !h.empty())
+        e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                               const msv_aln_item* items, uint64_t m, uint64_t workspace_bytes, int keep_posteriors,
+                               msv_aln_result** result) {
+    if (!p || !result || (n && !offsets) || (m && !items)) return MSV_ERR_INVALID_ARGUMENT;
+    *result = nullptr;
+    if (n >= (1ull << 32) || m >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
+    uint64_t longest = 0, total = 0;
+    msv_status s = n ? msvrt::csr_extent(offsets, n, &longest, &total) : MSV_OK;
+    if (s != MSV_OK) return s;
+    if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
+    if (longest >= (1ull << 31)) return MSV_ERR_SEQUENCE_TOO_LONG;
+    for (uint64_t q = 0; q < m; ++q) {
+        const msv_aln_item& it = items[q];
+        if (it.seq >= n || it.i_from < 1 || it.i_from > it.i_to || it.i_to > offsets[it.seq + 1] - offsets[it.seq])
+            return MSV_ERR_INVALID_ARGUMENT;
+    }
+    const alnk::AlnVariant* v = variant_of(p);
+    if (!v) return MSV_ERR_UNSUPPORTED_MODEL;
+    const uint64_t S = static_cast<uint64_t>(v->S);
+    const uint32_t M = p->model_length, K = M - 1;
+
+    auto* r = new (std::nothrow) msv_aln_result;
+    if (!r) return MSV_ERR_OUT_OF_MEMORY;
+    struct Guard {
+        msv_aln_result* r;
+        ~Guard() { delete r; }
+    } guard{r};
+    r->M = M;
+    r->kept = keep_posteriors != 0;
+    r->env.assign(m, std::nanf(""));
+    r->oa.assign(m, std::nanf(""));
+    r->dom_off.assign(m + 1, 0);
+    if (r->kept) {
+        r->pm.resize(m), r->pi.resize(m), r->pn.resize(m), r->pj.resize(m), r->pc.resize(m);
+    }
+    auto give = [&](msv_status st) {
+        *result = r;
+        guard.r = nullptr;
+        return st;
+    };
+    if (m == 0) return give(MSV_OK);
+
+    // the items as a batch of their own, and the chunks, before anything is launched
+    const uint64_t budget = workspace_bytes ? workspace_bytes : kDefaultWorkspace;
+    std::vector<uint64_t> poff(m + 1, 0), bytes(m), cuts(m + 1, 0), base(m);
+    std::vector<uint32_t> lc(m), sel(m);
+    for (uint64_t q = 0; q < m; ++q) {
+        const uint64_t Le = items[q].i_to - items[q].i_from + 1;
+        poff[q + 1] = poff[q] + Le;
+        bytes[q] = msv_host::aln_item_bytes(S, Le);
+        lc[q] = static_cast<uint32_t>(offsets[items[q].seq + 1] - offsets[items[q].seq]);
+        sel[q] = static_cast<uint32_t>(q);
+    }
+    uint64_t n_chunks = 0;
+    s = msv_vit_trace_chunk_cuts(bytes.data(), m, budget, cuts.data(), &n_chunks);
+    if (s == MSV_ERR_OUT_OF_MEMORY) return give(s);  // (nothing launched: the result says so, chunks = 0)
+    if (s != MSV_OK) return s;
+    std::vector<uint8_t> packed(poff[m]);
+    for (uint64_t q = 0; q < m; ++q)
+        std::copy_n(residues + offsets[items[q].seq] + items[q].i_from - 1, poff[q + 1] - poff[q],
+                    packed.begin() + static_cast<std::ptrdiff_t>(poff[q]));
+    uint64_t chunk_words = 0;
+    std::vector<uint32_t> counts(n_chunks);
+    for (uint64_t c = 0; c < n_chunks; ++c) {
+        uint64_t at = 0;
+        for (uint64_t q = cuts[c]; q < cuts[c + 1]; ++q) {
+            base[q] = at;
+            at += bytes[q] / 4;
+        }
+        chunk_words = std::max(chunk_words, at);
+        counts[c] = static_cast<uint32_t>(cuts[c + 1] - cuts[c]);
+    }
+
+    DeviceGuard g(p->device);
+    if (!g.ok) return MSV_ERR_NO_DEVICE;
+    if ((s = msv_dom_profile_reserve_length(p, longest)) != MSV_OK) return s;
+    hipStream_t st = p->stream;
+    msvrt::CsrStaging& sg = p->staged;
+    const std::vector<uint32_t> gates =
+        msv_host::aln_gates(p->tsc.data(), M, p->tr_B_Mk, v->S);
+    DeviceBuffer<uint32_t> d_ws, d_lc, d_sel, d_counts, d_gates, d_wcounts;
+    DeviceBuffer<uint64_t> d_base, d_domoff, d_opsoff;
+    DeviceBuffer<float> d_oa, d_oppp;
+    DeviceBuffer<msv_aln_item> d_items;
+    DeviceBuffer<msv_vit_domain> d_doms;
+    DeviceBuffer<uint8_t> d_ops;
+    msvrt::Event ev[8];
+    for (auto& e : ev) MSV_HIP(e.create(hipEventDefault));
+    MSV_HIP(sg.d_scores.reserve(m));
+    MSV_HIP(d_oa.reserve(m));
+    MSV_HIP(d_ws.reserve(chunk_words));
+    MSV_HIP(d_wcounts.reserve(2 * static_cast<size_t>(*std::max_element(counts.begin(), counts.end()))));
+    msvrt::StreamDrain drain(st);
+    MSV_HIP(sg.upload(packed.data(), poff.data(), 0, m, true, st, st));
+    MSV_HIP(upload(d_lc, lc, st));
+    MSV_HIP(upload(d_sel, sel, st));
+    MSV_HIP(upload(d_counts, counts, st));
+    MSV_HIP(upload(d_gates, gates, st));
+    MSV_HIP(upload(d_base, base, st));
+    MSV_HIP(d_items.reserve(m));
+    MSV_HIP(hipMemcpyAsync(d_items, items, m * sizeof(msv_aln_item), hipMemcpyHostToDevice, st));
+    // an item the kernels refuse keeps what is set here: NaN scores
+    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sg.d_scores.get()), 0x7fc00000, m, st));
+    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_oa.get()), 0x7fc00000, m, st));
+
+    alnk::AlnArgs a{};
+    a.etab = p->d_etab;
+    a.itab = p->d_itab ? p->d_itab.get() : p->d_etab.get();
+    a.gates = d_gates;
+    a.residues = sg.d_res;
+    a.offsets = sg.d_off;
+    a.lc = d_lc;
+    a.base = d_base;
+    a.lentab = p->d_lentab;
+    a.scores = sg.d_scores;
+    a.oa_scores = d_oa;
+    a.ws = d_ws;
+    a.errors = p->d_words + kHostErrWord;
+    a.n = m;
+    a.lentab_n = p->lentab_n;
+    a.tBM = p->tBM;
+    a.tEC = p->tEC;
+    a.tEJ = p->tEJ;
+    a.open_EC = std::isfinite(p->tr_E_C) ? 1u : 0u;
+    a.open_EJ = std::isfinite(p->tr_E_J) ? 1u : 0u;
+
+    std::vector<uint32_t> wc;
+    std::vector<uint64_t> doff, ooff;
+    std::vector<uint32_t> host_ws;
+    std::vector<msv_vit_domain> cdoms;
+    for (uint64_t c = 0; c < n_chunks; ++c) {
+        const uint64_t lo = cuts[c], hi = cuts[c + 1], cnt = hi - lo;
+        a.select = d_sel + lo;
+        a.select_count = d_counts + c;
+        MSV_HIP(hipEventRecord(ev[0], st));
+        a.ttab = p->d_ttab;
+        a.scan = p->d_scan;
+        if ((s = run_kernel(p, v->fwd_fn, v->waves, st, cnt, a)) != MSV_OK) return s;
+        MSV_HIP(hipEventRecord(ev[1], st));
+        a.ttab = p->d_btab;
+        a.scan = p->d_bscan;
+        if ((s = run_kernel(p, v->bck_fn, v->waves, st, cnt, a)) != MSV_OK) return s;
+        MSV_HIP(hipEventRecord(ev[2], st));
+        if ((s = run_kernel(p, v->fill_fn, alnk::kFillWaves, st, cnt, a)) != MSV_OK) return s;
+        MSV_HIP(hipEventRecord(ev[3], st));
+        alnk::WalkArgs w{};
+        w.ws = d_ws;
+        w.base = d_base;
+        w.offsets = sg.d_off;
+        w.scores = sg.d_scores;
+        w.oa_scores = d_oa;
+        w.items = d_items;
+        w.lo = static_cast<uint32_t>(lo);
+        w.hi = static_cast<uint32_t>(hi);
+        w.S = static_cast<uint32_t>(S);
+        w.counts = d_wcounts;
+        MSV_HIP(alnk::launch_walk(w, st));
+        MSV_HIP(hipEventRecord(ev[4], st));
+        wc.assign(2 * cnt, 0);
+        MSV_HIP(hipMemcpyAsync(wc.data(), d_wcounts, 2 * cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MSV_HIP(hipStreamSynchronize(st));
+        doff.assign(cnt + 1, 0);
+        ooff.assign(cnt + 1, 0);
+        for (uint64_t j = 0; j < cnt; ++j) {
+            doff[j + 1] = doff[j] + wc[2 * j];
+            ooff[j + 1] = ooff[j] + wc[2 * j + 1];
+        }
+        const uint64_t nd = doff[cnt], no = ooff[cnt];
+        const uint64_t ops0 = r->ops.size(), dom0 = r->domains.size();
+        MSV_HIP(upload(d_domoff, doff, st));
+        MSV_HIP(upload(d_opsoff, ooff, st));
+        MSV_HIP(d_doms.reserve(nd));
+        MSV_HIP(d_ops.reserve(no));
+        MSV_HIP(d_oppp.reserve(no));
+        w.dom_off = d_domoff;
+        w.ops_off = d_opsoff;
+        w.domains = d_doms;
+        w.ops = d_ops;
+        w.op_pp = d_oppp;
+        MSV_HIP(hipEventRecord(ev[5], st));
+        if (nd) MSV_HIP(alnk::launch_walk(w, st));
+        MSV_HIP(hipEventRecord(ev[6], st));
+        r->domains.resize(dom0 + nd);
+        r->ops.resize(ops0 + no);
+        r->op_pp.resize(ops0 + no);
+        if (nd) {
+            MSV_HIP(hipMemcpyAsync(r->domains.data() + dom0, d_doms, nd * sizeof(msv_vit_domain), hipMemcpyDeviceToHost,
+                                   st));
+            MSV_HIP(hipMemcpyAsync(r->ops.data() + ops0, d_ops, no, hipMemcpyDeviceToHost, st));
+            MSV_HIP(hipMemcpyAsync(r->op_pp.data() + ops0, d_oppp, no * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        uint64_t words = 0;
+        for (uint64_t q = lo; q < hi; ++q) words += bytes[q] / 4;
+        if (r->kept) {
+            host_ws.resize(words);
+            MSV_HIP(hipMemcpyAsync(host_ws.data(), d_ws, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
+        MSV_HIP(hipMemcpyAsync(r->env.data() + lo, sg.d_scores + lo, cnt * sizeof(float), hipMemcpyDeviceToHost, st));
+        MSV_HIP(hipMemcpyAsync(r->oa.data() + lo, d_oa + lo, cnt * sizeof(float), hipMemcpyDeviceToHost, st));
+        MSV_HIP(hipStreamSynchronize(st));  // the next chunk rewrites the workspace; the times are read per chunk
+        r->stats.forward_ms += elapsed(ev[0], ev[1]);
+        r->stats.backward_ms += elapsed(ev[1], ev[2]);
+        r->stats.fill_ms += elapsed(ev[2], ev[3]);
+        r->stats.walk_ms += elapsed(ev[3], ev[4]) + elapsed(ev[5], ev[6]);
+        r->stats.chunks += 1;
+        for (uint64_t j = 0; j < cnt; ++j) {
+            r->dom_off[lo + j + 1] = dom0 + doff[j + 1];
+            r->stats.matrix_bytes += 4 * msv_host::aln_matrix_words(S, poff[lo + j + 1] - poff[lo + j]);
+        }
+        for (uint64_t d = dom0; d < dom0 + nd; ++d) r->domains[d].ops_begin += ops0;
+        if (r->kept)
+            for (uint64_t q = lo; q < hi; ++q) {
+                const uint64_t Le = poff[q + 1] - poff[q];
+                r->pm[q].assign(Le * M, 0.0f);
+                r->pi[q].assign(Le * M, 0.0f);
+                r->pn[q].assign(Le, 0.0f);
+                r->pj[q].assign(Le, 0.0f);
+                r->pc[q].assign(Le, 0.0f);
+                if (!std::isfinite(r->env[q])) continue;
+                const uint32_t* rec = host_ws.data() + base[q];
+                const float* mat = reinterpret_cast<const float*>(rec + msv_host::aln_record_words(Le));
+                for (uint64_t i = 0; i < Le; ++i) {
+                    std::memcpy(&r->pn[q][i], rec + (i + 1) * 6 + 0, 4);
+                    std::memcpy(&r->pj[q][i], rec + (i + 1) * 6 + 1, 4);
+                    std::memcpy(&r->pc[q][i], rec + (i + 1) * 6 + 2, 4);
+                    const float* row = mat + i * 2 * S * 64;
+                    for (uint32_t k = 1; k <= K; ++k) {
+                        const uint64_t l = (k - 1) / S, sl = (k - 1) % S;
+                        r->pm[q][i * M + k] = row[sl * 64 + l];
+                        r->pi[q][i * M + k] = row[(S + sl) * 64 + l];
+                    }
+                }
+            }
+    }
+    drain.disarm();
+    s = stagedev::read_errors(p, kHostErrWord, st);
+    if (s != MSV_OK && s != MSV_ERR_BAD_RESIDUE && s != MSV_ERR_SEQUENCE_TOO_LONG) return s;
+    return give(s);
+}
+
+uint64_t msv_aln_result_count(const msv_aln_result* r) { return r ? r->env.size() : 0; }
+uint64_t msv_aln_result_domains(const msv_aln_result* r) { return r ? r->domains.size() : 0; }
+uint64_t msv_aln_result_ops(const msv_aln_result* r) { return r ? r->ops.size() : 0; }
+
+msv_status msv_aln_result_copy(const msv_aln_result* r, float* envelope_scores, float* oa_scores,
+                               uint64_t* domain_offsets, msv_vit_domain* domains, uint8_t* ops, float* op_pp) {
+    if (!r) return MSV_ERR_INVALID_ARGUMENT;
+    if (envelope_scores) std::copy(r->env.begin(), r->env.end(), envelope_scores);
+    if (oa_scores) std::copy(r->oa.begin(), r->oa.end(), oa_scores);
+    if (domain_offsets) std::copy(r->dom_off.begin(), r->dom_off.end(), domain_offsets);
+    if (domains) std::copy(r->domains.begin(), r->domains.end(), domains);
+    if (ops) std::copy(r->ops.begin(), r->ops.end(), ops);
+    if (op_pp) std::copy(r->op_pp.begin(), r->op_pp.end(), op_pp);
+    return MSV_OK;
+}
+
+msv_status msv_aln_result_posteriors(const msv_aln_result* r, uint64_t q, float* ppM, float* ppI, float* ppN,
+                                     float* ppJ, float* ppC) {
+    if (!r || !r->kept || q >= r->pm.size()) return MSV_ERR_INVALID_ARGUMENT;
+    if (ppM) std::copy(r->pm[q].begin(), r->pm[q].end(), ppM);
+    if (ppI) std::copy(r->pi[q].begin(), r->pi[q].end(), ppI);
+    if (ppN) std::copy(r->pn[q].begin(), r->pn[q].end(), ppN);
+    if (ppJ) std::copy(r->pj[q].begin(), r->pj[q].end(), ppJ);
+    if (ppC) std::copy(r->pc[q].begin(), r->pc[q].end(), ppC);
+    return MSV_OK;
+}
+
+void msv_aln_result_free(msv_aln_result* r) { delete r; }
+
+msv_status msv_aln_result_stats(const msv_aln_result* r, msv_aln_stats* out) {
+    if (!r || !out) return MSV_ERR_INVALID_ARGUMENT;
+    *out = r->stats;
+    return MSV_OK;
+}
+
+msv_status msv_aln_describe(const msv_dom_profile* p, msv_aln_info* out) {
+    if (!p || !out || out->struct_size < sizeof(uint32_t)) return MSV_ERR_INVALID_ARGUMENT;
+    const alnk::AlnVariant* v = variant_of(p);
+    if (!v) return MSV_ERR_UNSUPPORTED_MODEL;
+    DeviceGuard g(p->device);
+    if (!g.ok) return MSV_ERR_NO_DEVICE;
+    msv_aln_info info;
+    std::memset(&info, 0, sizeof(info));
+    info.states_per_lane = static_cast<uint32_t>(v->S);
+    info.pointer_words = static_cast<uint32_t>(msv_host::aln_pointer_words(static_cast<uint64_t>(v->S)));
+    info.forward_blocks = full_grid(p->device, v->fwd_fn, v->waves);
+    info.backward_blocks = full_grid(p->device, v->bck_fn, v->waves);
+    info.fill_blocks = full_grid(p->device, v->fill_fn, alnk::kFillWaves);
+    info.default_workspace_bytes = kDefaultWorkspace;
+    std::snprintf(info.variant, sizeof(info.variant), "%s", v->name);
+    hipFuncAttributes fa{};
+    if (hipFuncGetAttributes(&fa, v->fwd_fn) == hipSuccess) {
+        info.forward_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
+        info.forward_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
+    }
+    if (hipFuncGetAttributes(&fa, v->bck_fn) == hipSuccess) {
+        info.backward_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
+        info.backward_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
+    }
+    if (hipFuncGetAttributes(&fa, v->fill_fn) == hipSuccess) {
+        info.fill_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
+        info.fill_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
+    }
+    if (hipFuncGetAttributes(&fa, alnk::walk_fn()) == hipSuccess) {
+        info.walk_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
+        info.walk_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
+    }
+    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(info)));
+    info.struct_size = size;
+    std::memcpy(out, &info, size);
+    return MSV_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@
 
 #include "dom_host.h"
 #include "dom_kernel.h"
+#include "dom_profile.h"
 #include "hip_rt.h"
 #include "msv.h"
 #include "msv_kernel.h"
@@ -26,20 +27,6 @@ using msvrt::DeviceGuard;
 using msvrt::hip_status;
 using stagedev::kErrWord;
 using stagedev::kHostErrWord;
-
-struct msv_dom_profile : stagedev::StageProfile {
-    float tBM = 0, tEC = 0, tEJ = 0;  // odds of tr_B_Mk, tr_E_C, tr_E_J
-    const domk::DomVariant* v = nullptr;
-    DeviceBuffer<float> d_scan;       // Forward's scan multipliers
-    DeviceBuffer<float2> d_btab;      // Backward slot arrays [8][S/2][64]
-    DeviceBuffer<float> d_bscan;      // the mirrored scan's multipliers
-    uint32_t bck_blocks = 0;          // persistent grid of a full Backward launch
-    // msv_dom_decode_batch's buffers
-    DeviceBuffer<float> d_bck, d_begin, d_end, d_occ;
-    DeviceBuffer<uint32_t> d_records, d_sel, d_counts, d_rcount;
-    DeviceBuffer<uint64_t> d_rows, d_roff;
-    DeviceBuffer<msv_dom_region> d_regions;
-};
 
 struct msv_dom_result {
     std::vector<float> fwd, bck, begin, end, occ;
@@ -192,6 +179,9 @@ msv_status msv_dom_profile_create(int device, const float* match_scores, const f
                               p->tBM = odds(tr_B_Mk);
                               p->tEC = odds(tr_E_C);
                               p->tEJ = odds(tr_E_J);
+                              p->tr_B_Mk = tr_B_Mk;
+                              p->tr_E_C = tr_E_C;
+                              p->tr_E_J = tr_E_J;
                               const msv_status si = install(p, v);
                               return si == MSV_OK
                                          ? msv_dom_profile_reserve_length(p, stagedev::kDefaultMaxLength - 1)

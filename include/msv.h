@@ -638,8 +638,8 @@ msv_status msv_fwd_filter_batch(msv_profile* msv, msv_vit_profile* vit, msv_fwd_
  * else if start is unset, start = j; then, if occ[j] >= rt1, triggered.  While triggered: if
  * occ[j] - end[j] < rt2, the region (start, j) is emitted, start unset, triggered cleared.  A region open
  * at L is not emitted.  Each region carries two serial float sums over its residues in index order:
- * expected_domains = sum begin, mass = sum occ.  Resolving a region with expected_domains well above 1
- * into single domains (stochastic clustering, null2, per-envelope rescoring) is not part of this stage.
+ * expected_domains = sum begin, mass = sum occ.  Rescoring and aligning an envelope is the alignment stage's
+ * (below); splitting a region with expected_domains well above 1 by stochastic clustering, and null2, are not done.
  * The CPU function runs all this serially in float64 (odds rescaled by 2^256, as msv_fwd_cpu_score) and is
  * the reference of every test.  The device computes float32 odds rescaled by exact powers of two, Forward
  * and Backward each with its own running exponent; the exponents combine exactly, and for every residue
@@ -771,6 +771,131 @@ typedef struct msv_dom_stats {
     uint32_t reserved;
 } msv_dom_stats;
 msv_status msv_dom_result_stats(const msv_dom_result* result, msv_dom_stats* out);
+
+/* ---- Alignment stage: posterior decoding and the optimal-accuracy alignment of an envelope ----
+ * What a search reports for a domain: the envelope's own score, its alignment to the model chosen over ALL
+ * alignments (not read off the single best path), and how sure each aligned residue is.  This is HMMER3's
+ * rescore_isolated_domain: Forward and Backward on the envelope, posterior decoding of every (residue, state)
+ * cell, the optimal-accuracy (OA) alignment over those posteriors, and its trace.
+ * An ITEM is an envelope: residues i_from .. i_to (1-based, inclusive) of sequence seq, Le = i_to - i_from + 1,
+ * decoded as a sequence of its own of Le residues whose loop / move are those of a CONFIGURED length Lc
+ * (msv_sequence_transitions(Lc)).  The batch call sets Lc to the parent sequence's length (HMMER never
+ * reconfigures the model for an envelope); the CPU functions take Lc.  With Lc = Le an item is a whole sequence
+ * and everything below reduces to the Forward and domain blocks above.  With f, b the Forward and Backward odds
+ * of those blocks on the Le residues and Z = fC(Le) move:
+ *   envelope score = log Z (nats).  HMMER's per-domain score adds (Lc - Le) log(loop), the flanks emitted by N / C.
+ *   ppM(i,k) = fM(i,k) bM(i,k) / Z   k = 1..LENG;     ppI(i,k) = fI(i,k) bI(i,k) / Z   k = 1..LENG-1   (D is not decoded)
+ *   ppN(i) = fN(i-1) loop bN(i) / Z, likewise ppJ(i), ppC(i): the three terms of 1 - occ(i).  i = 1..Le.
+ * Rows are not renormalised: sum_k (ppM + ppI) + ppN + ppJ + ppC = 1 in exact arithmetic.
+ * Optimal accuracy, in float32 on float32 posteriors.  A transition is OPEN if its score is finite; "x via t" is
+ * x if t is open, else -inf.  Everything is -inf at row 0 except N(0) = 0 and B(0) = 0 via move.  Row i = 1..Le:
+ *   M(i,k) = max(M(i-1,k-1) via tMM[k-1], I(i-1,k-1) via tIM[k-1], D(i-1,k-1) via tDM[k-1], B(i-1) via tBM) + ppM(i,k)
+ *   I(i,k) = max(M(i-1,k) via tMI[k], I(i-1,k) via tII[k]) + ppI(i,k)
+ *   D(i,k) = max(M(i,k-1) via tMD[k-1], D(i,k-1) via tDD[k-1])
+ *   E(i) = max_k M(i,k);  N(i) = N(i-1) + ppN(i);  J(i) = max(J(i-1) + ppJ(i), E(i) via tEJ)
+ *   C(i) = max(C(i-1) + ppC(i), E(i) via tEC);  B(i) = max(N(i), J(i)) via move
+ * The OA score is C(Le), the expected number of correctly labelled residues; accuracy = score / Le.  E takes M
+ * only, and that is exact even though Forward counts the D -> E exits: D adds nothing, so a D value on a row is,
+ * bit for bit, some M value of the same row to its left, and no D exceeds the row's best M.  It also keeps the
+ * trace convention that a domain's first and last op are 'M'.  Each cell is one max and one float add, so the
+ * CPU and the GPU agree BIT FOR BIT on the same posterior arrays.  Tie-breaks are the Viterbi trace's: M takes
+ * M, I, D, B in that order; I takes M before I; D takes M before D; E the smallest k with M(i,k) == E(i); C and
+ * J the loop before E; B takes N before J; the source of a cell is the first candidate in that order that equals
+ * the max.  The trace is reported as msv_vit_domain records and op bytes as the Viterbi trace's (an OA path that
+ * passes through J yields several domains, all reported), and each op also carries one float32: the posterior of
+ * its cell (ppM for 'M', ppI for 'I', 0 for 'D').
+ * Tolerances.  The device decodes in float32 odds as the domain stage does and combines a cell as
+ * (float) ldexp((double) f (double) b invZ, e_f(i) + e_b(i) - e_f(Le)) with invZ = 1 / (double) Z: the product of
+ * two float32 is exact in float64, the exponents combine in an exact ldexp in float64's range (no pair of
+ * exponents loses range), and the one float32 rounding of a value <= 1 is at most 2^-24.  For every posterior
+ *   |gpu - cpu64| <= 48 (Le + LENG) 2^-24 + 2 2^-24     absolute
+ * (each of f, b, 1/Z carries Forward's relative 16 (Le + LENG) 2^-24, every posterior is <= 1; 1 2^-24 for the
+ * final rounding, 1 2^-24 covers the float64 roundings and the reference's own).  The OA score against
+ * msv_aln_cpu_align: |gpu - cpu| <= Le (posterior bound) + Le^2 2^-24 (a path sums Le posteriors, each within
+ * the bound; Le float32 adds of partial sums <= Le).  The envelope score has Forward's bound; with Lc = Le it is
+ * the Forward kernel's score of the same variant bit for bit.  Paths are compared exactly, and only against
+ * msv_aln_oa on the device's own posteriors.  null2 / bias corrections and the stochastic clustering of regions
+ * with expected_domains well above 1 are not part of this stage. */
+typedef struct msv_aln_item {
+    uint32_t seq;                  /* index of the parent sequence in the batch                     */
+    uint32_t i_from, i_to;         /* 1-based first and last residue of the envelope                */
+} msv_aln_item;
+typedef struct msv_aln_result msv_aln_result;
+
+/* The serial float64 decode of one envelope (rescaled as msv_dom_cpu_decode), model arguments as
+ * msv_fwd_cpu_score: *score = log Z; ppM, ppI double [Le][LENG + 1] (row i - 1, column k; column 0 is 0);
+ * ppN, ppJ, ppC double [Le].  Any output may be NULL.  Le = 0 gives -inf and writes nothing else; Lc < Le gives
+ * MSV_ERR_INVALID_ARGUMENT, a code >= 20 MSV_ERR_BAD_RESIDUE. */
+msv_status msv_aln_cpu_decode(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                              uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                              uint64_t Le, uint64_t Lc, double* score, double* ppM, double* ppI, double* ppN,
+                              double* ppJ, double* ppC);
+/* THE definition of the OA alignment and its walk, on float32 posteriors laid out as msv_aln_cpu_decode's (ppM,
+ * ppI float [Le][LENG + 1]).  Two calls size the output as msv_vit_cpu_trace: with domains, ops and op_pp NULL
+ * only *oa_score and the counts are written; then domains[*n_domains] (seq = 0, i relative to the envelope,
+ * ops_begin from 0), ops[*n_ops] and op_pp[*n_ops].  A score that is not finite (no open path to C) has no
+ * domains.  The device kernels reproduce this function exactly on the same arrays. */
+msv_status msv_aln_oa(const float* ppM, const float* ppI, const float* ppN, const float* ppJ, const float* ppC,
+                      const float* transition_scores, uint32_t model_length, float tr_B_Mk, float tr_E_C,
+                      float tr_E_J, uint64_t Le, uint64_t Lc, float* oa_score, uint32_t* n_domains, uint64_t* n_ops,
+                      msv_vit_domain* domains, uint8_t* ops, float* op_pp);
+/* The CPU twin of the whole stage for one item: the float64 decode, rounded to float32 once, then msv_aln_oa. */
+msv_status msv_aln_cpu_align(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                             uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                             uint64_t Le, uint64_t Lc, double* score, float* oa_score, uint32_t* n_domains,
+                             uint64_t* n_ops, msv_vit_domain* domains, uint8_t* ops, float* op_pp);
+/* Workspace bytes of one item of Le residues under a variant of S = states_per_lane: Le + 1 six-word records,
+ * Le rows of 2 S x 64 floats (Forward's fM, fI, then ppM, ppI in place), Le rows of ceil(S / 8) x 64 back-pointer
+ * words and Le row records (the Viterbi trace's encoding).  Chunks are cut by msv_vit_trace_chunk_cuts. */
+uint64_t msv_aln_item_bytes(uint32_t states_per_lane, uint64_t Le);
+
+/* Aligns envelopes of a host batch on the device (aln_kernel.hip), synchronous: per chunk of items a recording
+ * Forward launch (the full fM / fI matrix), a Backward launch that turns it into posteriors in place, an OA fill
+ * launch and two walk launches.  The host packs the items' residues into a CSR batch of their own and uploads
+ * only those.  Results are per item, in the caller's order; an item may repeat.  seq >= n, i_from < 1,
+ * i_to > L or i_from > i_to gives MSV_ERR_INVALID_ARGUMENT before any launch; workspace_bytes bounds the device
+ * workspace (0 = 1 GiB) and an item that alone exceeds it gives MSV_ERR_OUT_OF_MEMORY before any launch.
+ * MSV_ERR_BAD_RESIDUE is reported as msv_dom_decode_batch reports it and *result is still returned: the
+ * offending items have their score's error class and no domains, the others are aligned.  Domains carry the
+ * parent's seq and residues relative to the parent.  With keep_posteriors the device's posteriors are kept on
+ * the host: 8 Le (LENG + 1) + 12 Le bytes per item. */
+msv_status msv_aln_align_batch(msv_dom_profile* profile, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                               const msv_aln_item* items, uint64_t n_items, uint64_t workspace_bytes,
+                               int keep_posteriors, msv_aln_result** result);
+uint64_t msv_aln_result_count(const msv_aln_result* result);      /* items */
+uint64_t msv_aln_result_domains(const msv_aln_result* result);    /* domains in all */
+uint64_t msv_aln_result_ops(const msv_aln_result* result);        /* op bytes in all */
+/* envelope_scores[count], oa_scores[count], domain_offsets[count + 1], domains[], ops[], op_pp[]; any may be NULL. */
+msv_status msv_aln_result_copy(const msv_aln_result* result, float* envelope_scores, float* oa_scores,
+                               uint64_t* domain_offsets, msv_vit_domain* domains, uint8_t* ops, float* op_pp);
+/* Item q's posteriors as the device computed them (keep_posteriors, else MSV_ERR_INVALID_ARGUMENT): ppM, ppI
+ * float [Le][LENG + 1] as msv_aln_oa takes them, ppN, ppJ, ppC float [Le]; any may be NULL.  An item that was
+ * not decoded (its envelope score not finite) has zeros. */
+msv_status msv_aln_result_posteriors(const msv_aln_result* result, uint64_t q, float* ppM, float* ppI, float* ppN,
+                                     float* ppJ, float* ppC);
+void msv_aln_result_free(msv_aln_result* result);
+
+/* Append-only, as msv_dom_info. */
+typedef struct msv_aln_info {
+    uint32_t struct_size;
+    uint32_t states_per_lane;
+    uint32_t pointer_words;            /* uint32 of back-pointers per lane and row                 */
+    uint32_t forward_blocks, backward_blocks, fill_blocks;   /* persistent grids of full launches */
+    uint32_t forward_scratch_bytes, backward_scratch_bytes, fill_scratch_bytes, walk_scratch_bytes;
+    uint32_t forward_lds_bytes, backward_lds_bytes, fill_lds_bytes, walk_lds_bytes;
+    uint64_t default_workspace_bytes;
+    char variant[64];
+} msv_aln_info;
+msv_status msv_aln_describe(const msv_dom_profile* profile, msv_aln_info* out);
+
+/* What the call did on the device: its chunks, the matrix bytes the recording launches wrote, and the summed
+ * device times of the four launch kinds (HIP events; the walk's two launches together). */
+typedef struct msv_aln_stats {
+    uint64_t chunks;
+    uint64_t matrix_bytes;
+    float forward_ms, backward_ms, fill_ms, walk_ms;
+} msv_aln_stats;
+msv_status msv_aln_result_stats(const msv_aln_result* result, msv_aln_stats* out);
 
 #ifdef __cplusplus
 } /* extern "C" */
