@@ -3,12 +3,13 @@
 //
 // One envelope per 64-lane wave, lane l holds the S consecutive states l*S+1 .. l*S+S, in dom_kernel.hip's shape
 // (its variant family, its table placement per S, the work queue of seq_queue.h).  Four launch kinds per chunk:
-//   aln_fwd_kernel   dom_fwd_kernel's row restated, statement for statement, plus the stores: after every row each
-//                    lane stores its S values of fM and of fI (float bits, in the scale of the row's exponent) as
-//                    [row][slot][lane] -- a store instruction writes 256 contiguous bytes -- next to the six-word
-//                    special-state record.  loop / move are those of the item's CONFIGURED length lc[s].
-//   aln_bck_kernel   dom_bck_kernel's row; once bM and bI of row i stand, the lane loads the row's fM and fI and
-//                    writes ppM and ppI over them: (float) ldexp((double) f * (double) b * invZ, ef(i) + eb - ef(Le)).
+//   aln_fwd_kernel   the Forward row of p7_forward_row.inc (fwd_kernel's and dom_fwd_kernel's) plus the stores: after
+//                    every row each lane stores its S values of fM and of fI (float bits, in the scale of the row's
+//                    exponent) as [row][slot][lane] -- a store instruction writes 256 contiguous bytes -- next to the
+//                    six-word special-state record.  loop / move are those of the item's CONFIGURED length lc[s].
+//   aln_bck_kernel   the Backward row of p7_backward_*.inc (dom_bck_kernel's); once bM and bI of row i stand, the
+//                    lane loads the row's fM and fI and writes ppM and ppI over them:
+//                    (float) ldexp((double) f * (double) b * invZ, ef(i) + eb - ef(Le)).
 //                    The product of two floats is exact in float64, the ldexp is applied to the product (whose
 //                    true value is <= 1), so no pair of exponents loses range.  Lane 0 writes ppN, ppJ, ppC of
 //                    residue i + 1 over the first three words of row i + 1's record, which Backward has read.
@@ -28,45 +29,17 @@
 #include "aln_host.h"
 #include "aln_kernel.h"
 #include "msv_kernel.h"
-#include "seq_queue.h"
+#include "p7_rows.h"
 #include "vit_trace_plan.h"
 
 namespace alnk {
 
 namespace {
 
-using domk::B_DD;
-using domk::B_DM;
-using domk::B_II;
-using domk::B_IM;
-using domk::B_MD;
-using domk::B_MI;
-using domk::B_MM;
-using domk::B_SFX;
-
 constexpr float NINF = -__builtin_inff();
 
-constexpr int DPP_WAVE_SHR1 = 0x138;
-constexpr int DPP_WAVE_SHL1 = 0x130;
-__device__ __forceinline__ float shift1(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), DPP_WAVE_SHR1, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float shift1_down(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), DPP_WAVE_SHL1, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float shift_by(float v, int lane, int d) {
-    const float t = __int_as_float(__builtin_amdgcn_ds_bpermute((lane - d) * 4, __float_as_int(v)));
-    return lane >= d ? t : 0.0f;
-}
-__device__ __forceinline__ float shift_down_by(float v, int lane, int d) {
-    const float t = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane + d) & 63) * 4, __float_as_int(v)));
-    return lane + d < kLanes ? t : 0.0f;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
+using p7::shift1;  // (the fill shifts M, I, D by one state as Forward does)
+
 __device__ __forceinline__ float wave_max(float x) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) x = fmaxf(x, __shfl_xor(x, d, 64));
@@ -85,40 +58,11 @@ __device__ __forceinline__ bool not_finite(uint32_t bits) { return (bits & 0x7f8
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-// The recording Forward kernel: dom_fwd_kernel's body plus the matrix stores.
+// The recording Forward kernel: the shared head, start and row (p7_rows.h), the record and the matrix stores.
 // ------------------------------------------------------------------------------------------------
 template <int S, bool ELDS, bool ISC, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void aln_fwd_kernel(const AlnArgs a) {
-    static_assert(S >= 2 && S % 2 == 0, "S must be even");
-    constexpr int C2 = S / 2;
-    constexpr int ROW2 = C2 * kLanes;
-    constexpr bool FENCE = S > 12;
-    enum : int { MM_IN = 0, IM_IN = 1, DM_IN = 2, MI = 3, II = 4, MD_IN = 5, DD_IN = 6, DC = 7 };  // fwdk::
-    __shared__ float2 etab_s[ELDS ? kRows * ROW2 : 1];
-    __shared__ float2 ttab_s[kArrays * ROW2];
-    __shared__ uint32_t exited_s;
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t total = seqq::list_total(a);
-    if (static_cast<uint64_t>(blockIdx.x) * WAVES >= total) {
-        if (threadIdx.x == 0) seqq::count_leavers<1, 1>(a.counter);
-        return;
-    }
-
-    if constexpr (ELDS)
-        for (int i = threadIdx.x; i < kRows * ROW2; i += WAVES * 64) etab_s[i] = a.etab[i];
-    for (int i = threadIdx.x; i < kArrays * ROW2; i += WAVES * 64) ttab_s[i] = a.ttab[i];
-    if (threadIdx.x == 0) exited_s = 0;
-    __syncthreads();
-
-    float A[kScanSteps];
-#pragma unroll
-    for (int j = 0; j < kScanSteps; ++j) A[j] = a.scan[j * kLanes + lane];
-    uint32_t rz = 0;  // an opaque zero renewed every row (fwd_kernel.hip)
-    auto tlds = [&](int j, int c) -> float2 { return ttab_s[rz + (j * C2 + c) * kLanes + lane]; };
-
-    const uint32_t nwaves = gridDim.x * WAVES;
-    uint32_t item = blockIdx.x * WAVES + wave;
+#include "p7_kernel_head.inc"
     while (item < total) {
         uint32_t s;
         uint64_t o0, L;
@@ -126,12 +70,7 @@ __global__ __launch_bounds__(WAVES * 64) void aln_fwd_kernel(const AlnArgs a) {
             const uint32_t lc = __builtin_amdgcn_readfirstlane(a.lc[s]);
             const float2 lm = a.lentab[lc];
             const float loop = lm.x, move = lm.y;
-            float M[S], I[S], D[S];
-#pragma unroll
-            for (int q = 0; q < S; ++q) M[q] = I[q] = D[q] = 0.0f;
-            float N = 1.0f, J = 0.0f, Cc = 0.0f, B = move;
-            int32_t e2 = 0;
-            uint32_t maxcode = 0;
+#include "p7_forward_begin.inc"
             uint32_t* rec = a.ws + seqq::u64first(a.base[s]);
             float* mat = reinterpret_cast<float*>(rec + (L + 1) * kRowWords) + lane;  // row i at mat + i * 2 S 64
             auto record = [&](float E) {
@@ -146,94 +85,11 @@ __global__ __launch_bounds__(WAVES * 64) void aln_fwd_kernel(const AlnArgs a) {
                 rec += kRowWords;
             };
             record(0.0f);  // row 0
+            // the first two residue blocks: `cur` is the block of the row, `nxt` the one after it
             const uint8_t* res = a.residues + o0;
-            uint32_t cur = static_cast<uint64_t>(lane) < L ? res[lane] : 0u;
-            uint32_t nxt = static_cast<uint64_t>(64 + lane) < L ? res[64 + lane] : 0u;
+            uint32_t cur = p7::residue_at(res, L, lane), nxt = p7::residue_at(res, L, 64 + lane);
             for (uint64_t i = 0; i < L; ++i) {
-                const uint32_t ph = static_cast<uint32_t>(i) & 63u;
-                if (ph == 0 && i != 0) {
-                    cur = nxt;
-                    nxt = (i + 64 + lane < L) ? res[i + 64 + lane] : 0u;
-                }
-                uint32_t code = __builtin_amdgcn_readlane(cur, ph);
-                maxcode = code > maxcode ? code : maxcode;
-                code = code < 19u ? code : 19u;
-                asm volatile("" : "+v"(rz));
-                const float Bt = B * a.tBM;
-                const float2* er;
-                if constexpr (ELDS) er = etab_s + code * ROW2 + lane;
-                else er = a.etab + code * ROW2 + lane;
-                const float2* ir = a.itab + code * ROW2 + lane;
-
-                const float sM = shift1(M[S - 1]), sI = shift1(I[S - 1]), sD = shift1(D[S - 1]);
-                float Es = 0.0f;
-#pragma unroll
-                for (int c = C2 - 1; c >= 0; --c) {
-                    const float2 tmm = tlds(MM_IN, c), tim = tlds(IM_IN, c), tdm = tlds(DM_IN, c);
-                    const float2 tmi = tlds(MI, c), tii = tlds(II, c);
-                    const float2 e = er[c * kLanes];
-                    float2 ins = {1.0f, 1.0f};
-                    if constexpr (ISC) ins = ir[c * kLanes];
-#pragma unroll
-                    for (int h = 1; h >= 0; --h) {
-                        const int q = 2 * c + h;
-                        float iv = fmaf(I[q], h ? tii.y : tii.x, M[q] * (h ? tmi.y : tmi.x));
-                        if constexpr (ISC) iv = iv * (h ? ins.y : ins.x);
-                        const float pm = q ? M[q - 1] : sM, pi = q ? I[q - 1] : sI, pd = q ? D[q - 1] : sD;
-                        const float acc = fmaf(pd, h ? tdm.y : tdm.x,
-                                               fmaf(pi, h ? tim.y : tim.x, pm * (h ? tmm.y : tmm.x)));
-                        const float m = (h ? e.y : e.x) * (acc + Bt);
-                        M[q] = m;
-                        I[q] = iv;
-                        Es += m;
-                    }
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-                const float sMn = shift1(M[S - 1]);
-#pragma unroll
-                for (int c = 0; c < C2; ++c) {
-                    const float2 tmd = tlds(MD_IN, c), tdd = tlds(DD_IN, c);
-                    D[2 * c] = c ? fmaf(D[2 * c - 1], tdd.x, M[2 * c - 1] * tmd.x) : sMn * tmd.x;
-                    D[2 * c + 1] = fmaf(D[2 * c], tdd.y, M[2 * c] * tmd.y);
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-                float b = D[S - 1];
-                b = fmaf(A[0], shift1(b), b);
-#pragma unroll
-                for (int j = 1; j < kScanSteps; ++j) b = fmaf(A[j], shift_by(b, lane, 1 << j), b);
-                const float Din = shift1(b);
-#pragma unroll
-                for (int c = 0; c < C2; ++c) {
-                    const float2 dc = tlds(DC, c);
-                    D[2 * c] = fmaf(Din, dc.x, D[2 * c]);
-                    D[2 * c + 1] = fmaf(Din, dc.y, D[2 * c + 1]);
-                    Es += D[2 * c];
-                    Es += D[2 * c + 1];
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-                float E = wave_sum(Es);
-                N = N * loop;
-                J = fmaf(J, loop, E * a.tEJ);
-                Cc = fmaf(Cc, loop, E * a.tEC);
-                B = (N + J) * move;
-                const uint32_t Eb = __builtin_amdgcn_readfirstlane(__float_as_uint(E));
-                if (Eb > 0x4f800000u && Eb < 0x7f800000u) {  // 2^32 < E < inf
-                    uint32_t x = (Eb >> 23) - 127u;
-                    x = x < 126u ? x : 126u;
-                    const float down = __uint_as_float((127u - x) << 23);
-#pragma unroll
-                    for (int q = 0; q < S; ++q) {
-                        M[q] *= down;
-                        I[q] *= down;
-                        D[q] *= down;
-                    }
-                    N *= down;
-                    J *= down;
-                    Cc *= down;
-                    B *= down;
-                    E *= down;  // (recorded only)
-                    e2 += static_cast<int32_t>(x);
-                }
+#include "p7_forward_row.inc"
                 record(E);  // row i + 1, in the scale of its exponent
                 // the row's fM and fI, in that scale too: [slot][lane], 256 contiguous bytes a store
                 float* mrow = mat + i * (2 * S * kLanes);
@@ -243,24 +99,11 @@ __global__ __launch_bounds__(WAVES * 64) void aln_fwd_kernel(const AlnArgs a) {
                     mrow[(S + q) * kLanes] = I[q];
                 }
             }
-            const float sc = fmaf(static_cast<float>(e2), 0.69314718055994529f, logf(Cc * move));
-            if (lane == 0) {
-                if (maxcode >= 20u) {
-                    a.scores[s] = __builtin_inff();
-                    atomicOr(a.errors, msvk::kErrBadResidue);
-                } else {
-                    a.scores[s] = sc;
-                }
-            }
+#include "p7_forward_end.inc"
         }
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(a.counter, 1u);
-        item = nwaves + __builtin_amdgcn_readfirstlane(t);
+        item = seqq::next_item(a.counter, lane, nwaves);
     }
-    if (lane == 0) {
-        __threadfence();
-        if (atomicAdd(&exited_s, 1u) == WAVES - 1) seqq::count_leavers<1, 1>(a.counter);
-    }
+    seqq::last_exit<WAVES>(a.counter, &exited_s, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -268,35 +111,7 @@ __global__ __launch_bounds__(WAVES * 64) void aln_fwd_kernel(const AlnArgs a) {
 // ------------------------------------------------------------------------------------------------
 template <int S, bool ELDS, bool ISC, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void aln_bck_kernel(const AlnArgs a) {
-    static_assert(S >= 2 && S % 2 == 0, "S must be even");
-    constexpr int C2 = S / 2;
-    constexpr int ROW2 = C2 * kLanes;
-    constexpr bool FENCE = S > 12;
-    __shared__ float2 etab_s[ELDS ? kRows * ROW2 : 1];
-    __shared__ float2 ttab_s[kArrays * ROW2];
-    __shared__ uint32_t exited_s;
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t total = seqq::list_total(a);
-    if (static_cast<uint64_t>(blockIdx.x) * WAVES >= total) {
-        if (threadIdx.x == 0) seqq::count_leavers<1, 1>(a.counter);
-        return;
-    }
-
-    if constexpr (ELDS)
-        for (int i = threadIdx.x; i < kRows * ROW2; i += WAVES * 64) etab_s[i] = a.etab[i];
-    for (int i = threadIdx.x; i < kArrays * ROW2; i += WAVES * 64) ttab_s[i] = a.ttab[i];
-    if (threadIdx.x == 0) exited_s = 0;
-    __syncthreads();
-
-    float A[kScanSteps];
-#pragma unroll
-    for (int j = 0; j < kScanSteps; ++j) A[j] = a.scan[j * kLanes + lane];
-    uint32_t rz = 0;
-    auto tlds = [&](int j, int c) -> float2 { return ttab_s[rz + (j * C2 + c) * kLanes + lane]; };
-
-    const uint32_t nwaves = gridDim.x * WAVES;
-    uint32_t item = blockIdx.x * WAVES + wave;
+#include "p7_kernel_head.inc"
     while (item < total) {
         const uint32_t s = __builtin_amdgcn_readfirstlane(a.select[item]);
         const uint32_t fwd_bits = s < a.n ? __builtin_amdgcn_readfirstlane(__float_as_uint(a.scores[s])) : 0x7fc00000u;
@@ -312,74 +127,12 @@ __global__ __launch_bounds__(WAVES * 64) void aln_bck_kernel(const AlnArgs a) {
             // Z = fC(L) move 2^efL, its reciprocal taken once in float64
             const double invZ = 1.0 / static_cast<double>(__uint_as_float(rec0[L * kRowWords + 2]) * move);
             const int32_t efL = static_cast<int32_t>(rec0[L * kRowWords + 5]);
-            float M[S], I[S], D[S];
-#pragma unroll
-            for (int q = 0; q < S; ++q) M[q] = I[q] = D[q] = 0.0f;
-            float bJ = 0.0f, bC = 0.0f, bN = 0.0f;
-            int32_t e2 = 0;  // the values are the true ones times 2^-e2
-            const uint8_t* res = a.residues + o0;
-            const uint64_t top = (L - 1) >> 6;
-            uint32_t cur = (top * 64 + lane < L) ? res[top * 64 + lane] : 0u;
-            uint32_t nxt = top ? res[(top - 1) * 64 + lane] : 0u;
+#include "p7_backward_begin.inc"
             for (uint64_t i = L + 1; i-- > 0;) {
                 const uint32_t* const r6 = rec0 + i * kRowWords;
                 const float fN = __uint_as_float(r6[0]), fJ = __uint_as_float(r6[1]), fC = __uint_as_float(r6[2]);
                 const int32_t ef = static_cast<int32_t>(r6[5]);
-                uint32_t code = 0;
-                if (i < L) {
-                    const uint32_t ph = static_cast<uint32_t>(i) & 63u;
-                    if (ph == 63u && i != L - 1) {
-                        cur = nxt;
-                        nxt = (i >= 127) ? res[((i >> 6) - 1) * 64 + lane] : 0u;
-                    }
-                    code = __builtin_amdgcn_readlane(cur, ph);
-                    code = code < 19u ? code : 19u;
-                }
-                asm volatile("" : "+v"(rz));
-                const float2* er;
-                if constexpr (ELDS) er = etab_s + code * ROW2 + lane;
-                else er = a.etab + code * ROW2 + lane;
-                const float2* ir = a.itab + code * ROW2 + lane;
-
-                float Ps = 0.0f;
-#pragma unroll
-                for (int c = 0; c < C2; ++c) {
-                    const float2 e = er[c * kLanes];
-                    M[2 * c] = e.x * M[2 * c];
-                    M[2 * c + 1] = e.y * M[2 * c + 1];
-                    Ps += M[2 * c];
-                    Ps += M[2 * c + 1];
-                    if constexpr (ISC) {
-                        const float2 ins = ir[c * kLanes];
-                        I[2 * c] = ins.x * I[2 * c];
-                        I[2 * c + 1] = ins.y * I[2 * c + 1];
-                    }
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-                float sigma = wave_sum(Ps);
-                const uint32_t Sb = __builtin_amdgcn_readfirstlane(__float_as_uint(sigma));
-                if (Sb > 0x4f800000u && Sb < 0x7f800000u) {  // 2^32 < sigma < inf
-                    uint32_t x = (Sb >> 23) - 127u;
-                    x = x < 126u ? x : 126u;
-                    const float down = __uint_as_float((127u - x) << 23);
-#pragma unroll
-                    for (int q = 0; q < S; ++q) {
-                        M[q] *= down;
-                        I[q] *= down;
-                    }
-                    bJ *= down;
-                    bC *= down;
-                    bN *= down;
-                    sigma *= down;
-                    e2 += static_cast<int32_t>(x);
-                }
-                const float bB = sigma * a.tBM;
-                const float lJ = bJ * loop, lC = bC * loop, lN = bN * loop;
-                const float mB = move * bB;
-                bJ = lJ + mB;
-                bN = lN + mB;
-                bC = i == L ? move : lC;
-                const float bE = fmaf(bJ, a.tEJ, a.tEC * bC);
+#include "p7_backward_specials.inc"
 
                 // residue i + 1 emitted by N, J or C: over the first three words of row i + 1's record, which the
                 // previous iteration read (before the passes over the slots, as dom_bck_kernel places its own)
@@ -394,43 +147,7 @@ __global__ __launch_bounds__(WAVES * 64) void aln_bck_kernel(const AlnArgs a) {
                         ldexp(static_cast<double>(fC) * static_cast<double>(lC) * invZ, sh)));
                 }
 
-                const float gTop = shift1_down(M[0]);
-#pragma unroll
-                for (int c = C2 - 1; c >= 0; --c) {
-                    const float2 tdm = tlds(B_DM, c), tdd = tlds(B_DD, c);
-                    const float g1 = (c == C2 - 1) ? gTop : M[2 * c + 2];
-                    const float u1 = fmaf(tdm.y, g1, bE);
-                    D[2 * c + 1] = (c == C2 - 1) ? u1 : fmaf(tdd.y, D[2 * c + 2], u1);
-                    const float x0 = (c == 0 && lane == 0) ? 0.0f : bE;
-                    D[2 * c] = fmaf(tdd.x, D[2 * c + 1], fmaf(tdm.x, M[2 * c + 1], x0));
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-                float b = D[0];
-                b = fmaf(A[0], shift1_down(b), b);
-#pragma unroll
-                for (int j = 1; j < kScanSteps; ++j) b = fmaf(A[j], shift_down_by(b, lane, 1 << j), b);
-                const float Din = shift1_down(b);
-#pragma unroll
-                for (int c = 0; c < C2; ++c) {
-                    const float2 sf = tlds(B_SFX, c);
-                    D[2 * c] = fmaf(Din, sf.x, D[2 * c]);
-                    D[2 * c + 1] = fmaf(Din, sf.y, D[2 * c + 1]);
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int c = 0; c < C2; ++c) {
-                    const float2 tmm = tlds(B_MM, c), tmi = tlds(B_MI, c), tmd = tlds(B_MD, c);
-                    const float2 tim = tlds(B_IM, c), tii = tlds(B_II, c);
-                    const float g0 = M[2 * c + 1];
-                    const float g1 = (c == C2 - 1) ? gTop : M[2 * c + 2];
-                    const float d1 = (c == C2 - 1) ? Din : D[2 * c + 2];
-                    const float h0 = I[2 * c], h1 = I[2 * c + 1];
-                    M[2 * c] = fmaf(tmd.x, D[2 * c + 1], fmaf(tmi.x, h0, fmaf(tmm.x, g0, bE)));
-                    I[2 * c] = fmaf(tii.x, h0, tim.x * g0);
-                    M[2 * c + 1] = fmaf(tmd.y, d1, fmaf(tmi.y, h1, fmaf(tmm.y, g1, bE)));
-                    I[2 * c + 1] = fmaf(tii.y, h1, tim.y * g1);
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
+#include "p7_backward_cells.inc"
                 // the combine: row i's fM, fI become ppM, ppI in place, two slots at a time
                 if (i >= 1) {
                     float* mrow = mat + (i - 1) * (2 * S * kLanes);
@@ -450,14 +167,9 @@ __global__ __launch_bounds__(WAVES * 64) void aln_bck_kernel(const AlnArgs a) {
                 }
             }
         }
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(a.counter, 1u);
-        item = nwaves + __builtin_amdgcn_readfirstlane(t);
+        item = seqq::next_item(a.counter, lane, nwaves);
     }
-    if (lane == 0) {
-        __threadfence();
-        if (atomicAdd(&exited_s, 1u) == WAVES - 1) seqq::count_leavers<1, 1>(a.counter);
-    }
+    seqq::last_exit<WAVES>(a.counter, &exited_s, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -473,7 +185,7 @@ __global__ __launch_bounds__(kFillWaves * 64) void aln_fill_kernel(const AlnArgs
     const int lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint64_t total = seqq::list_total(a);
-    if (static_cast<uint64_t>(blockIdx.x) * kFillWaves >= total) {
+    if (seqq::no_item<kFillWaves>(total)) {
         if (threadIdx.x == 0) seqq::count_leavers<1, 1>(a.counter);
         return;
     }
@@ -596,14 +308,9 @@ __global__ __launch_bounds__(kFillWaves * 64) void aln_fill_kernel(const AlnArgs
             }
             if (lane == 0) a.oa_scores[s] = C;
         }
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(a.counter, 1u);
-        item = nwaves + __builtin_amdgcn_readfirstlane(t);
+        item = seqq::next_item(a.counter, lane, nwaves);
     }
-    if (lane == 0) {
-        __threadfence();
-        if (atomicAdd(&exited_s, 1u) == kFillWaves - 1) seqq::count_leavers<1, 1>(a.counter);
-    }
+    seqq::last_exit<kFillWaves>(a.counter, &exited_s, lane);
 }
 
 // ------------------------------------------------------------------------------------------------

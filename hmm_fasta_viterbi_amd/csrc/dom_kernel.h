@@ -6,14 +6,15 @@
 
 #include <cstdint>
 
+#include "fwd_kernel.h"
 #include "msv.h"
 
 namespace domk {
 
-constexpr int kRows = 20;      // residue rows of the odds tables
-constexpr int kArrays = 8;     // per-slot arrays of ttab (fwd_kernel.h's) and of btab (below)
-constexpr int kLanes = 64;     // one sequence per wave
-constexpr int kScanSteps = 6;  // log2(kLanes) steps of either D chain's cross-lane scan
+using fwdk::kArrays;     // per-slot arrays of ttab (fwd_kernel.h's) and of btab (below)
+using fwdk::kLanes;
+using fwdk::kRows;
+using fwdk::kScanSteps;  // steps of either D chain's cross-lane scan
 constexpr int kRowWords = 6;   // a Forward record: N, J, C, B, E (float bits) and the running exponent (int32)
 
 // Backward slot arrays (odds, 0 where the transition does not exist), per lane slot q (state k = lane * S + q + 1):

@@ -21,203 +21,40 @@
 // A sequence is computed by one wave in a fixed operation order, so its score does not depend on its place in
 // the batch, on the select list or on the stream.  Variants differ in S, that is in the order of summation, so
 // their scores may differ in the last bits.
+// The row and the kernel's frame are written once, in p7_rows.h and the text it documents (p7_kernel_head.inc,
+// p7_forward_begin.inc, p7_forward_row.inc, p7_forward_end.inc): the domain and the alignment stage record this
+// very row.
 #include <hip/hip_runtime.h>
 
 #include "fwd_host.h"
 #include "fwd_kernel.h"
 #include "msv_kernel.h"
-#include "seq_queue.h"
+#include "p7_rows.h"
 
 namespace fwdk {
 
-namespace {
-
-// Lane l-1's value into lane l, 0 into lane 0: one DPP move across the wave (wave_shr:1, bound_ctrl off: the
-// lane without a source keeps `old`, which is 0).
-constexpr int DPP_WAVE_SHR1 = 0x138;
-__device__ __forceinline__ float shift1(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), DPP_WAVE_SHR1, 0xF, 0xF, false));
-}
-// Lane l-d's value into lane l (d = 2 .. 32), 0 into lanes below d: ds_bpermute_b32 (the LDS crossbar, no LDS
-// memory) and a select.
-__device__ __forceinline__ float shift_by(float v, int lane, int d) {
-    const float t = __int_as_float(__builtin_amdgcn_ds_bpermute((lane - d) * 4, __float_as_int(v)));
-    return lane >= d ? t : 0.0f;
-}
-// The 64-lane sum as a butterfly: every lane adds the same pairs in the same order, so all lanes hold the same
-// bits (a + b == b + a).
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-}  // namespace
-
+// Nothing is this kernel's own but the order of the shared pieces: the recording kernels add their stores to it.
 template <int S, bool ELDS, bool ISC, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void fwd_kernel(const FwdArgs a) {
-    static_assert(S >= 2 && S % 2 == 0, "S must be even");
-    constexpr int C2 = S / 2;
-    constexpr int ROW2 = C2 * kLanes;  // float2 per table row
-    // long rows: every chunk its own scheduling region, or the scheduler hoists a whole row of loads and spills
-    constexpr bool FENCE = S > 12;
-    __shared__ float2 etab_s[ELDS ? kRows * ROW2 : 1];
-    __shared__ float2 ttab_s[kArrays * ROW2];
-    __shared__ uint32_t exited_s;
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t total = seqq::list_total(a);
-    if (static_cast<uint64_t>(blockIdx.x) * WAVES >= total) {
-        // no sequence for this workgroup (a device-count launch is sized for n): leave, counted like any other
-        if (threadIdx.x == 0) seqq::count_leavers<1, 1>(a.counter);
-        return;
-    }
-
-    if constexpr (ELDS)
-        for (int i = threadIdx.x; i < kRows * ROW2; i += WAVES * 64) etab_s[i] = a.etab[i];
-    for (int i = threadIdx.x; i < kArrays * ROW2; i += WAVES * 64) ttab_s[i] = a.ttab[i];
-    if (threadIdx.x == 0) exited_s = 0;
-    __syncthreads();
-
-    float A[kScanSteps];  // this lane's multiplier of every scan step, in VGPRs for the whole launch
-#pragma unroll
-    for (int j = 0; j < kScanSteps; ++j) A[j] = a.scan[j * kLanes + lane];
-    // `rz` is an opaque zero renewed every row: without it the compiler hoists the loop-invariant LDS loads of
-    // the slot arrays out of the row loop into VGPRs and spills them
-    uint32_t rz = 0;
-    auto tlds = [&](int j, int c) -> float2 { return ttab_s[rz + (j * C2 + c) * kLanes + lane]; };
-
-    const uint32_t nwaves = gridDim.x * WAVES;
-    uint32_t item = blockIdx.x * WAVES + wave;
+#include "p7_kernel_head.inc"
     while (item < total) {
         uint32_t s;
         uint64_t o0, L;
         if (seqq::take(a, item, lane, &s, &o0, &L)) {
             const float2 lm = a.lentab[L];
             const float loop = lm.x, move = lm.y;
-            // everything a sequence carries starts here: M, I, D, the specials and the scale's exponent
-            float M[S], I[S], D[S];
-#pragma unroll
-            for (int q = 0; q < S; ++q) M[q] = I[q] = D[q] = 0.0f;
-            float N = 1.0f, J = 0.0f, Cc = 0.0f, B = move;
-            int32_t e2 = 0;  // the values are the true ones times 2^-e2
-            uint32_t maxcode = 0;
+#include "p7_forward_begin.inc"
+            // the first two residue blocks: `cur` is the block of the row, `nxt` the one after it
             const uint8_t* res = a.residues + o0;
-            uint32_t cur = static_cast<uint64_t>(lane) < L ? res[lane] : 0u;
-            uint32_t nxt = static_cast<uint64_t>(64 + lane) < L ? res[64 + lane] : 0u;
+            uint32_t cur = p7::residue_at(res, L, lane), nxt = p7::residue_at(res, L, 64 + lane);
             for (uint64_t i = 0; i < L; ++i) {
-                const uint32_t ph = static_cast<uint32_t>(i) & 63u;
-                if (ph == 0 && i != 0) {
-                    cur = nxt;
-                    nxt = (i + 64 + lane < L) ? res[i + 64 + lane] : 0u;
-                }
-                uint32_t code = __builtin_amdgcn_readlane(cur, ph);
-                maxcode = code > maxcode ? code : maxcode;
-                code = code < 19u ? code : 19u;
-                asm volatile("" : "+v"(rz));
-                const float Bt = B * a.tBM;
-                const float2* er;
-                if constexpr (ELDS) er = etab_s + code * ROW2 + lane;
-                else er = a.etab + code * ROW2 + lane;
-                const float2* ir = a.itab + code * ROW2 + lane;
-
-                // the previous row's last states, from the lane on the left (k - 1 across the boundary)
-                const float sM = shift1(M[S - 1]), sI = shift1(I[S - 1]), sD = shift1(D[S - 1]);
-                // M/I pass, highest slot first, in place: I(k) reads M'(k), I'(k); M(k) reads M'(k-1), I'(k-1),
-                // D'(k-1).  The B term is added last.
-                float Es = 0.0f;
-#pragma unroll
-                for (int c = C2 - 1; c >= 0; --c) {
-                    const float2 tmm = tlds(MM_IN, c), tim = tlds(IM_IN, c), tdm = tlds(DM_IN, c);
-                    const float2 tmi = tlds(MI, c), tii = tlds(II, c);
-                    const float2 e = er[c * kLanes];
-                    float2 ins = {1.0f, 1.0f};
-                    if constexpr (ISC) ins = ir[c * kLanes];
-#pragma unroll
-                    for (int h = 1; h >= 0; --h) {
-                        const int q = 2 * c + h;
-                        float iv = fmaf(I[q], h ? tii.y : tii.x, M[q] * (h ? tmi.y : tmi.x));
-                        if constexpr (ISC) iv = iv * (h ? ins.y : ins.x);
-                        const float pm = q ? M[q - 1] : sM, pi = q ? I[q - 1] : sI, pd = q ? D[q - 1] : sD;
-                        const float acc = fmaf(pd, h ? tdm.y : tdm.x,
-                                               fmaf(pi, h ? tim.y : tim.x, pm * (h ? tmm.y : tmm.x)));
-                        const float m = (h ? e.y : e.x) * (acc + Bt);
-                        M[q] = m;
-                        I[q] = iv;
-                        Es += m;
-                    }
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-                // D pass, lowest slot first, each lane's chain started from an incoming 0
-                const float sMn = shift1(M[S - 1]);  // this row's M(k-1) for each lane's first slot
-#pragma unroll
-                for (int c = 0; c < C2; ++c) {
-                    const float2 tmd = tlds(MD_IN, c), tdd = tlds(DD_IN, c);
-                    D[2 * c] = c ? fmaf(D[2 * c - 1], tdd.x, M[2 * c - 1] * tmd.x) : sMn * tmd.x;
-                    D[2 * c + 1] = fmaf(D[2 * c], tdd.y, M[2 * c] * tmd.y);
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-                // the lanes' affine maps D_out = a D_in + b, scanned inclusively over the lanes: after step j,
-                // b is the lane's last D given an incoming 0 at lane l - 2^(j+1) + 1
-                float b = D[S - 1];
-                b = fmaf(A[0], shift1(b), b);
-#pragma unroll
-                for (int j = 1; j < kScanSteps; ++j) b = fmaf(A[j], shift_by(b, lane, 1 << j), b);
-                const float Din = shift1(b);  // the exact D entering this lane (0 into lane 0)
-#pragma unroll
-                for (int c = 0; c < C2; ++c) {
-                    const float2 dc = tlds(DC, c);
-                    D[2 * c] = fmaf(Din, dc.x, D[2 * c]);
-                    D[2 * c + 1] = fmaf(Din, dc.y, D[2 * c + 1]);
-                    Es += D[2 * c];
-                    Es += D[2 * c + 1];
-                    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-                }
-                // specials: E is the same in every lane (wave_sum), so J, C, N, B and the rescaling are uniform
-                const float E = wave_sum(Es);
-                N = N * loop;
-                J = fmaf(J, loop, E * a.tEJ);
-                Cc = fmaf(Cc, loop, E * a.tEC);
-                B = (N + J) * move;
-                const uint32_t Eb = __builtin_amdgcn_readfirstlane(__float_as_uint(E));  // (E >= 0: bits order as floats)
-                if (Eb > 0x4f800000u && Eb < 0x7f800000u) {  // 2^32 < E < inf
-                    // scale down by 2^-x, x = E's exponent (at most 126, so 2^-x is a normal float): exact
-                    uint32_t x = (Eb >> 23) - 127u;
-                    x = x < 126u ? x : 126u;
-                    const float down = __uint_as_float((127u - x) << 23);
-#pragma unroll
-                    for (int q = 0; q < S; ++q) {
-                        M[q] *= down;
-                        I[q] *= down;
-                        D[q] *= down;
-                    }
-                    N *= down;
-                    J *= down;
-                    Cc *= down;
-                    B *= down;
-                    e2 += static_cast<int32_t>(x);
-                }
+#include "p7_forward_row.inc"
             }
-            const float sc = fmaf(static_cast<float>(e2), 0.69314718055994529f, logf(Cc * move));
-            if (lane == 0) {
-                if (maxcode >= 20u) {
-                    a.scores[s] = __builtin_inff();
-                    atomicOr(a.errors, msvk::kErrBadResidue);
-                } else {
-                    a.scores[s] = sc;
-                }
-            }
+#include "p7_forward_end.inc"
         }
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(a.counter, 1u);
-        item = nwaves + __builtin_amdgcn_readfirstlane(t);
+        item = seqq::next_item(a.counter, lane, nwaves);
     }
-    // the last workgroup to finish resets the counters for the next launch on this profile (one grid-level
-    // atomic per workgroup, by its last wave, counted in LDS)
-    if (lane == 0) {
-        __threadfence();
-        if (atomicAdd(&exited_s, 1u) == WAVES - 1) seqq::count_leavers<1, 1>(a.counter);
-    }
+    seqq::last_exit<WAVES>(a.counter, &exited_s, lane);
 }
 
 namespace {

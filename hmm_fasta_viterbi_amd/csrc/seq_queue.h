@@ -7,7 +7,8 @@
 // counter[0], which starts at zero and hands out the grid's worker count + 0, 1, ...  counter[1] counts the
 // leavers; the last one puts the pair back to zero, so the slot's next launch needs no reset (launch_ring.h).
 // Refusals are latched as msvk::kErr* bits in `errors`.  `Args` is vitk::VitArgs or fwdk::FwdArgs, which name
-// these fields alike.  (The MSV kernels' queue -- per lane group, with `order` -- is another one.)
+// these fields alike; domk::DomArgs and alnk::AlnArgs do too.  (The MSV kernels' queue -- per lane group, with
+// `order` -- is another one.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -68,6 +69,33 @@ __device__ __forceinline__ bool take(const Args& a, uint32_t item, int lane, uin
         return true;
     }
     return false;
+}
+
+// The frame of a kernel whose workers are the single waves of workgroups of WAVES (`exited_s` a word of LDS, zeroed
+// before a workgroup barrier; nwaves = gridDim.x * WAVES):
+//     if (seqq::no_item<WAVES>(total)) { if (threadIdx.x == 0) seqq::count_leavers<1, 1>(a.counter); return; }
+//     uint32_t item = blockIdx.x * WAVES + wave;
+//     while (item < total) { ...; item = seqq::next_item(a.counter, lane, nwaves); }
+//     seqq::last_exit<WAVES>(a.counter, &exited_s, lane);
+// no_item: no entry is left for this workgroup (a device-count launch is sized for n): it leaves at once, counted like
+// any other.
+template <int WAVES>
+__device__ __forceinline__ bool no_item(uint64_t total) {
+    return static_cast<uint64_t>(blockIdx.x) * WAVES >= total;
+}
+__device__ __forceinline__ uint32_t next_item(uint32_t* counter, int lane, uint32_t nwaves) {
+    uint32_t t = 0;
+    if (lane == 0) t = atomicAdd(counter, 1u);
+    return nwaves + __builtin_amdgcn_readfirstlane(t);
+}
+// The last workgroup to finish resets the counters for the next launch on this profile (one grid-level atomic per
+// workgroup, by its last wave, counted in LDS)
+template <int WAVES>
+__device__ __forceinline__ void last_exit(uint32_t* counter, uint32_t* exited_s, int lane) {
+    if (lane == 0) {
+        __threadfence();
+        if (atomicAdd(exited_s, 1u) == WAVES - 1) count_leavers<1, 1>(counter);
+    }
 }
 
 }  // namespace seqq
