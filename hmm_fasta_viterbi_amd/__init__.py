@@ -735,10 +735,14 @@ class Alignments:
     Viterbi trace reports one (`domains`, DOMAIN_DTYPE records with the parent's seq and residues relative to the
     parent, entry q's are domains[domain_offsets[q]:domain_offsets[q+1]]; `ops`, one byte 'M' / 'I' / 'D' per core
     state visited) and `op_pp`, one float32 per op: the posterior of the op's cell (0 for 'D').  `status` is the
-    call's status name, `stats` what the device did."""
+    call's status name, `stats` what the device did.  Made with null2=True (msv.h "Bias stage") it also has `null2`
+    float32 [m, 20], the envelope's null2 odds of each residue, and `domcorrection` float32 [m] (nats), and
+    bias_scores gives the corrected bit scores and P-values; else both are None."""
 
     def __init__(self, items, envelope_scores, domain_scores, oa_scores, domain_offsets, domains, ops, op_pp, *,
-                 status="MSV_OK", stats=None, posteriors=None):
+                 status="MSV_OK", stats=None, posteriors=None, null2=None, domcorrection=None, parent_lengths=None):
+        self.null2, self.domcorrection = null2, domcorrection
+        self._parent_lengths = parent_lengths
         self.items = items
         self.envelope_scores, self.domain_scores, self.oa_scores = envelope_scores, domain_scores, oa_scores
         Le = (items["i_to"].astype(np.int64) - items["i_from"].astype(np.int64) + 1).astype(np.float32)
@@ -774,6 +778,39 @@ class Alignments:
         if self._posteriors is None:
             raise ValueError("these alignments were made without keep_posteriors")
         return self._posteriors[q]
+
+    def bias_scores(self, tau: float, lam: float, fwd_scores=None) -> dict:
+        """The bias-corrected scores (msv_aln_bias_scores; tau, lam = STATS LOCAL FORWARD): dombias, domain_bits
+        (float32 [m]) and domain_pvalues (float64 [m]).  With fwd_scores -- the Forward scores of the batch's
+        sequences, indexed as items["seq"] is -- also seq_bias, seq_bits, seq_pvalues over those sequences, each
+        sequence's bias taken from the summed corrections of its items."""
+        if self.domcorrection is None:
+            raise ValueError("these alignments were made without null2")
+        m = len(self)
+        Lc = np.ascontiguousarray(self._parent_lengths[self.items["seq"].astype(np.int64)] if m else [], np.uint64)
+        Le = np.ascontiguousarray(self.items["i_to"].astype(np.int64) - self.items["i_from"].astype(np.int64) + 1,
+                                  np.uint64)
+        env = np.ascontiguousarray(self.envelope_scores, np.float32)
+        dc = np.ascontiguousarray(self.domcorrection, np.float32)
+        parent = np.ascontiguousarray(self.items["seq"], np.uint32)
+        out = {"dombias": np.zeros(m, np.float32), "domain_bits": np.zeros(m, np.float32),
+               "domain_pvalues": np.zeros(m, np.float64)}
+        n_seq, fwd, lens = 0, None, None
+        if fwd_scores is not None:
+            fwd = np.ascontiguousarray(fwd_scores, np.float32)
+            n_seq = fwd.size
+            if n_seq != self._parent_lengths.size:
+                raise ValueError("fwd_scores must have one score per sequence of the batch")
+            lens = np.ascontiguousarray(self._parent_lengths, np.uint64)
+            out.update(seq_bias=np.zeros(n_seq, np.float32), seq_bits=np.zeros(n_seq, np.float32),
+                       seq_pvalues=np.zeros(n_seq, np.float64))
+        check(_native.lib().msv_aln_bias_scores(
+            _ptr(env), _ptr(Le), _ptr(Lc), _ptr(dc), m, _ptr(parent), None if fwd is None else _ptr(fwd),
+            None if lens is None else _ptr(lens), n_seq, tau, lam, _ptr(out["dombias"]), _ptr(out["domain_bits"]),
+            _ptr(out["domain_pvalues"]), *[_ptr(out[k]) if k in out else None
+                                           for k in ("seq_bias", "seq_bits", "seq_pvalues")]),
+            "msv_aln_bias_scores")
+        return out
 
 
 def aln_oa(ppM, ppI, ppN, ppJ, ppC, transition_scores, consts, Lc: int | None = None):
@@ -920,13 +957,15 @@ class Domain_HMM(_StageEngine):
 
     def align_batch(self, seqs: Sequence[str] | None = None, items=None, *, codes: np.ndarray | None = None,
                     offsets: np.ndarray | None = None, envelopes: "Envelopes | None" = None,
-                    workspace_bytes: int = 0, keep_posteriors: bool = False, strict: bool = True) -> Alignments:
-        """Posterior decoding and the optimal-accuracy alignment of envelopes, on the GPU (msv_aln_align_batch).
+                    workspace_bytes: int = 0, keep_posteriors: bool = False, strict: bool = True,
+                    null2: bool = False) -> Alignments:
+        """Posterior decoding and the optimal-accuracy alignment of envelopes, on the GPU (msv_aln_align_batch_opts).
         `items` are (seq, i_from, i_to) triples (1-based, inclusive) or ITEM_DTYPE records; envelopes= takes an
         Envelopes and aligns every region of it.  Each item is decoded as a sequence of its own whose loop / move are
         those of the parent's length.  workspace_bytes bounds the device workspace (0: 1 GiB); keep_posteriors keeps
         the device's posteriors on the host (8 Le (LENG + 1) bytes an item).  A bad residue inside an item raises
-        IndexError unless strict=False: then that item has no domains and `status` says so."""
+        IndexError unless strict=False: then that item has no domains and `status` says so.  null2=True also runs the
+        bias stage (msv.h "Bias stage"): the result carries `null2` and `domcorrection`, and bias_scores works."""
         codes, offsets, n = _batch(seqs, codes, offsets)
         if envelopes is not None:
             if items is not None:
@@ -951,15 +990,16 @@ class Domain_HMM(_StageEngine):
         it = np.ascontiguousarray(it)
         L = _native.lib()
         r = C.c_void_p()
-        st = L.msv_aln_align_batch(self._p, _ptr(codes), offsets.ctypes.data, n, _ptr(it), len(it), workspace_bytes,
-                                   1 if keep_posteriors else 0, C.byref(r))
+        opts = _native.AlnOptions(workspace_bytes, 1 if keep_posteriors else 0, 1 if null2 else 0)
+        st = L.msv_aln_align_batch_opts(self._p, _ptr(codes), offsets.ctypes.data, n, _ptr(it), len(it), C.byref(opts),
+                                        C.byref(r))
         if not r.value:
-            check(st, "msv_aln_align_batch")
+            check(st, "msv_aln_align_batch_opts")
         try:
             if st not in (_native.MSV_OK, _native.MSV_ERR_BAD_RESIDUE):
-                check(st, "msv_aln_align_batch")
+                check(st, "msv_aln_align_batch_opts")
             if strict:
-                _check_residues(st, "msv_aln_align_batch")
+                _check_residues(st, "msv_aln_align_batch_opts")
             m = L.msv_aln_result_count(r)
             env, oa = np.zeros(m, np.float32), np.zeros(m, np.float32)
             dom_off = np.zeros(m + 1, np.uint64)
@@ -980,24 +1020,40 @@ class Domain_HMM(_StageEngine):
                     post.append((pm, pi, pn, pj, pc))
             stats = _native.AlnStats()
             check(L.msv_aln_result_stats(r, C.byref(stats)))
+            stats = {f: getattr(stats, f) for f, _ in stats._fields_}
+            n2 = dc = None
+            if null2:
+                n2, dc = np.zeros((m, 20), np.float32), np.zeros(m, np.float32)
+                check(L.msv_aln_result_null2(r, _ptr(n2), _ptr(dc)), "msv_aln_result_null2")
+                ns = _native.AlnNull2Stats()
+                check(L.msv_aln_result_null2_stats(r, C.byref(ns)), "msv_aln_result_null2_stats")
+                stats.update(null2_ms=ns.null2_ms, null2_partial_ms=ns.partial_ms, null2_slab_bytes=ns.slab_bytes,
+                             null2_row_block=ns.row_block)
         finally:
             L.msv_aln_result_free(r)
-        Lc = np.diff(offsets.astype(np.int64))[it["seq"].astype(np.int64)] if m else np.zeros(0, np.int64)
+        lengths = np.diff(offsets.astype(np.int64))
+        Lc = lengths[it["seq"].astype(np.int64)] if m else np.zeros(0, np.int64)
         return Alignments(it, env, _domain_scores(env, Le, Lc), oa, dom_off, doms, ops, pp,
-                          status=_native.STATUS.get(st, str(st)),
-                          stats={f: getattr(stats, f) for f, _ in stats._fields_}, posteriors=post)
+                          status=_native.STATUS.get(st, str(st)), stats=stats, posteriors=post, null2=n2,
+                          domcorrection=dc, parent_lengths=lengths)
 
 
 def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Forward_HMM,
                     seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
                     offsets: np.ndarray | None = None, F1: float = 0.02, F2: float = 1e-3,
-                    dom_engine: "Domain_HMM | None" = None, F3: float = 1e-5, align: bool = False) -> dict:
+                    dom_engine: "Domain_HMM | None" = None, F3: float = 1e-5, align: bool = False,
+                    null2: bool = False) -> dict:
     """HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV over every sequence, P <= F1, Viterbi on the
     survivors, P <= F2, Forward on those, Forward P-values.  Returns the per-stage arrays: msv_scores, passed_msv,
     vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run).
     With dom_engine, also "envelopes": the Envelopes of the sequences with Forward P <= F3, in index order (a second
     call that uploads the batch again: Domain_HMM.decode_batch with select = those indices).  With align=True (which
-    needs dom_engine) also "alignments": Domain_HMM.align_batch of every region of those envelopes."""
+    needs dom_engine) also "alignments": Domain_HMM.align_batch of every region of those envelopes.  With null2=True
+    (which needs align=True) the alignments carry null2 (msv.h "Bias stage") and the dict gains domain_bits,
+    domain_pvalues (per alignment item) and seq_bias, seq_bits, seq_pvalues, indexed as the envelopes' sequences are
+    (entry q is sequence envelopes.select[q])."""
+    if null2 and not align:
+        raise ValueError("null2=True needs align=True")
     codes, offsets, n = _batch(seqs, codes, offsets)
     stats = np.array([msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
                       fwd_engine.forward_tau, fwd_engine.forward_lambda], np.float32)
@@ -1015,7 +1071,13 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
         hits = np.flatnonzero(p2.astype(bool) & (fpv <= F3)).astype(np.uint32)
         out["envelopes"] = dom_engine.decode_batch(codes=codes, offsets=offsets, select=hits)
         if align:
-            out["alignments"] = dom_engine.align_batch(codes=codes, offsets=offsets, envelopes=out["envelopes"])
+            out["alignments"] = dom_engine.align_batch(codes=codes, offsets=offsets, envelopes=out["envelopes"],
+                                                       null2=null2)
+            if null2:
+                b = out["alignments"].bias_scores(fwd_engine.forward_tau, fwd_engine.forward_lambda, fwd_scores=fsc)
+                out["domain_bits"], out["domain_pvalues"] = b["domain_bits"], b["domain_pvalues"]
+                for k in ("seq_bias", "seq_bits", "seq_pvalues"):
+                    out[k] = b[k][hits]
     elif align:
         raise ValueError("align=True needs dom_engine")
     return out

@@ -73,6 +73,8 @@ EXPORTED = [
     "msv_aln_cpu_decode", "msv_aln_oa", "msv_aln_cpu_align", "msv_aln_item_bytes", "msv_aln_align_batch",
     "msv_aln_result_count", "msv_aln_result_domains", "msv_aln_result_ops", "msv_aln_result_copy",
     "msv_aln_result_posteriors", "msv_aln_result_free", "msv_aln_describe", "msv_aln_result_stats",
+    "msv_aln_cpu_null2", "msv_aln_null2_correction", "msv_aln_bias_scores", "msv_aln_align_batch_opts",
+    "msv_aln_result_null2", "msv_aln_result_null2_stats",
 ]
 
 
@@ -212,6 +214,12 @@ class AlnInfo(C.Structure):
         ("walk_lds_bytes", C.c_uint32),
         ("default_workspace_bytes", C.c_uint64),
         ("variant", C.c_char * 64),
+        ("null2_row_block", C.c_uint32),
+        ("null2_partial_scratch_bytes", C.c_uint32),
+        ("null2_finish_scratch_bytes", C.c_uint32),
+        ("null2_partial_lds_bytes", C.c_uint32),
+        ("null2_finish_lds_bytes", C.c_uint32),
+        ("reserved", C.c_uint32),
     ]
 
     def __init__(self):
@@ -227,6 +235,25 @@ class AlnInfo(C.Structure):
 class AlnStats(C.Structure):
     _fields_ = [("chunks", C.c_uint64), ("matrix_bytes", C.c_uint64), ("forward_ms", C.c_float),
                 ("backward_ms", C.c_float), ("fill_ms", C.c_float), ("walk_ms", C.c_float)]
+
+
+class AlnOptions(C.Structure):
+    """msv_aln_options: append-only, struct_size first (set on construction)."""
+    _fields_ = [("struct_size", C.c_uint64), ("workspace_bytes", C.c_uint64), ("keep_posteriors", C.c_int32),
+                ("null2", C.c_int32)]
+
+    def __init__(self, workspace_bytes=0, keep_posteriors=0, null2=0):
+        super().__init__(C.sizeof(AlnOptions), workspace_bytes, keep_posteriors, null2)
+
+
+class AlnNull2Stats(C.Structure):
+    """msv_aln_null2_stats: append-only, struct_size first (set before the call)."""
+    _fields_ = [("struct_size", C.c_uint32), ("row_block", C.c_uint32), ("null2_ms", C.c_float),
+                ("partial_ms", C.c_float), ("slab_bytes", C.c_uint64)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(AlnNull2Stats)
 
 
 # msv_aln_item as a numpy structured dtype
@@ -457,6 +484,12 @@ def lib() -> C.CDLL:
         "msv_aln_result_free": (None, [vp]),
         "msv_aln_describe": (C.c_int, [vp, C.POINTER(AlnInfo)]),
         "msv_aln_result_stats": (C.c_int, [vp, C.POINTER(AlnStats)]),
+        "msv_aln_cpu_null2": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, u64, u64, vp, C.POINTER(C.c_double)]),
+        "msv_aln_null2_correction": (C.c_int, [vp, vp, u64, C.POINTER(f32)]),
+        "msv_aln_bias_scores": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, vp, u64, f32, f32, vp, vp, vp, vp, vp, vp]),
+        "msv_aln_align_batch_opts": (C.c_int, [vp, vp, vp, u64, vp, u64, C.POINTER(AlnOptions), C.POINTER(vp)]),
+        "msv_aln_result_null2": (C.c_int, [vp, vp, vp]),
+        "msv_aln_result_null2_stats": (C.c_int, [vp, C.POINTER(AlnNull2Stats)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

@@ -4,7 +4,9 @@
 // the tables the domain stage's variant installed, the fill kernel a small table of gate bytes made per call.  The
 // host packs the items' residues into a CSR batch of their own (item q is sequence q of it), cuts the items into
 // chunks that fit the workspace as the Viterbi trace's are cut, and runs five launches per chunk, each on its own
-// launch slot: recording Forward, Backward with the combine, OA fill, walk count, walk place.
+// launch slot: recording Forward, Backward with the combine, OA fill, walk count, walk place.  With the null2 option
+//  two more, plain launches of aln_null2.hip that only read the workspace, after the count walk: the
+// row-block partial sums into a slab buffer of the call's own, then one wave per item that finishes null2[20].
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,10 +18,12 @@
 
 #include "aln_host.h"
 #include "aln_kernel.h"
+#include "aln_null2.h"
 #include "dom_profile.h"
 #include "hip_rt.h"
 #include "msv.h"
 #include "msv_kernel.h"
+#include "null2_host.h"
 #include "stage_profile.h"
 
 using msvrt::DeviceBuffer;
@@ -37,6 +41,11 @@ struct msv_aln_result {
     uint32_t M = 0;
     std::vector<std::vector<float>> pm, pi, pn, pj, pc;
     msv_aln_stats stats{};
+    // the null2 option: per item null2 [20] and the correction (zeros where the item was not decoded)
+    bool has_null2 = false;
+    std::vector<float> null2, domcorr;
+    float null2_ms = 0.0f, null2_partial_ms = 0.0f;
+    uint64_t slab_bytes = 0;
 };
 
 namespace {
@@ -82,13 +91,9 @@ hipError_t upload(DeviceBuffer<T>& d, const std::vector<T>& h, hipStream_t st) {
     return e;
 }
 
-}  // namespace
-
-extern "C" {
-
-msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
-                               const msv_aln_item* items, uint64_t m, uint64_t workspace_bytes, int keep_posteriors,
-                               msv_aln_result** result) {
+msv_status align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                       const msv_aln_item* items, uint64_t m, uint64_t workspace_bytes, int keep_posteriors,
+                       bool null2, msv_aln_result** result) {
     if (!p || !result || (n && !offsets) || (m && !items)) return MSV_ERR_INVALID_ARGUMENT;
     *result = nullptr;
     if (n >= (1ull << 32) || m >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
@@ -115,6 +120,11 @@ msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, cons
     } guard{r};
     r->M = M;
     r->kept = keep_posteriors != 0;
+    r->has_null2 = null2;
+    if (null2) {
+        r->null2.assign(m * msv_host::kNull2Residues, 0.0f);
+        r->domcorr.assign(m, 0.0f);
+    }
     r->env.assign(m, std::nanf(""));
     r->oa.assign(m, std::nanf(""));
     r->dom_off.assign(m + 1, 0);
@@ -158,6 +168,28 @@ msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, cons
         chunk_words = std::max(chunk_words, at);
         counts[c] = static_cast<uint32_t>(cuts[c + 1] - cuts[c]);
     }
+    // null2: the units (item, block of kNull2RowBlock rows) of every chunk, chunk after chunk
+    const alnk::Null2Variant* nv = null2 ? alnk::null2_variant(v->S, v->isc) : nullptr;
+    if (null2 && !nv) return MSV_ERR_UNSUPPORTED_MODEL;
+    std::vector<uint32_t> unit_item, unit_first;
+    std::vector<uint64_t> unit_start;
+    uint64_t chunk_units = 0;
+    if (null2) {
+        unit_first.resize(m);
+        unit_start.assign(n_chunks + 1, 0);
+        for (uint64_t c = 0; c < n_chunks; ++c) {
+            uint64_t at = 0;
+            for (uint64_t q = cuts[c]; q < cuts[c + 1]; ++q) {
+                const uint64_t nb = msv_host::null2_blocks(poff[q + 1] - poff[q]);
+                if (at + nb >= (1ull << 32)) return give(MSV_ERR_OUT_OF_MEMORY);
+                unit_first[q] = static_cast<uint32_t>(at);
+                unit_item.insert(unit_item.end(), nb, static_cast<uint32_t>(q));
+                at += nb;
+            }
+            unit_start[c + 1] = unit_start[c] + at;
+            chunk_units = std::max(chunk_units, at);
+        }
+    }
 
     DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
@@ -172,8 +204,18 @@ msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, cons
     DeviceBuffer<msv_aln_item> d_items;
     DeviceBuffer<msv_vit_domain> d_doms;
     DeviceBuffer<uint8_t> d_ops;
-    msvrt::Event ev[8];
+    DeviceBuffer<uint32_t> d_unit_item, d_unit_first;
+    DeviceBuffer<float> d_slabs, d_null2;
+    msvrt::Event ev[8], ev_null2, ev_null2_mid;
     for (auto& e : ev) MSV_HIP(e.create(hipEventDefault));
+    if (null2) {
+        // the slabs are the call's own, about 1 / kNull2RowBlock of the matrix: never the caller's workspace
+        MSV_HIP(ev_null2.create(hipEventDefault));
+        MSV_HIP(ev_null2_mid.create(hipEventDefault));
+        MSV_HIP(d_slabs.reserve(chunk_units * msv_host::null2_slab_floats(S)));
+        MSV_HIP(d_null2.reserve(m * msv_host::kNull2Residues));
+        r->slab_bytes = chunk_units * msv_host::null2_slab_floats(S) * sizeof(float);
+    }
     MSV_HIP(sg.d_scores.reserve(m));
     MSV_HIP(d_oa.reserve(m));
     MSV_HIP(d_ws.reserve(chunk_words));
@@ -190,6 +232,23 @@ msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, cons
     // an item the kernels refuse keeps what is set here: NaN scores
     MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sg.d_scores.get()), 0x7fc00000, m, st));
     MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_oa.get()), 0x7fc00000, m, st));
+    alnk::Null2Args na{};
+    if (null2) {
+        MSV_HIP(upload(d_unit_item, unit_item, st));
+        MSV_HIP(upload(d_unit_first, unit_first, st));
+        // an item the kernels skip keeps what is set here: zeros
+        MSV_HIP(hipMemsetAsync(d_null2, 0, m * msv_host::kNull2Residues * sizeof(float), st));
+        na.ws = d_ws;
+        na.base = d_base;
+        na.offsets = sg.d_off;
+        na.scores = sg.d_scores;
+        na.unit_first = d_unit_first;
+        na.slabs = d_slabs;
+        na.etab = p->d_etab;
+        na.itab = p->d_itab ? p->d_itab.get() : p->d_etab.get();
+        na.null2 = d_null2;
+        na.leng = K;
+    }
 
     alnk::AlnArgs a{};
     a.etab = p->d_etab;
@@ -244,6 +303,16 @@ msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, cons
         w.counts = d_wcounts;
         MSV_HIP(alnk::launch_walk(w, st));
         MSV_HIP(hipEventRecord(ev[4], st));
+        if (null2) {  // behind the count walk, so that the four existing launch kinds keep their own event pairs
+            na.unit_item = d_unit_item + unit_start[c];
+            na.units = static_cast<uint32_t>(unit_start[c + 1] - unit_start[c]);
+            na.lo = static_cast<uint32_t>(lo);
+            na.hi = static_cast<uint32_t>(hi);
+            MSV_HIP(alnk::null2_launch_partial(nv, na, st));
+            MSV_HIP(hipEventRecord(ev_null2_mid, st));
+            MSV_HIP(alnk::null2_launch_finish(nv, na, st));
+            MSV_HIP(hipEventRecord(ev_null2, st));
+        }
         wc.assign(2 * cnt, 0);
         MSV_HIP(hipMemcpyAsync(wc.data(), d_wcounts, 2 * cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         MSV_HIP(hipStreamSynchronize(st));
@@ -291,6 +360,10 @@ msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, cons
         r->stats.fill_ms += elapsed(ev[2], ev[3]);
         r->stats.walk_ms += elapsed(ev[3], ev[4]) + elapsed(ev[5], ev[6]);
         r->stats.chunks += 1;
+        if (null2) {
+            r->null2_ms += elapsed(ev[4], ev_null2);
+            r->null2_partial_ms += elapsed(ev[4], ev_null2_mid);
+        }
         for (uint64_t j = 0; j < cnt; ++j) {
             r->dom_off[lo + j + 1] = dom0 + doff[j + 1];
             r->stats.matrix_bytes += 4 * msv_host::aln_matrix_words(S, poff[lo + j + 1] - poff[lo + j]);
@@ -320,10 +393,67 @@ msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, cons
                 }
             }
     }
+    if (null2) {
+        MSV_HIP(hipMemcpyAsync(r->null2.data(), d_null2, r->null2.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        MSV_HIP(hipStreamSynchronize(st));
+        // THE definition of the correction, on the device's own null2: the device's domcorrection has its bits
+        for (uint64_t q = 0; q < m; ++q)
+            if (std::isfinite(r->env[q]))
+                r->domcorr[q] = msv_host::null2_correction(r->null2.data() + q * msv_host::kNull2Residues,
+                                                           packed.data() + poff[q], poff[q + 1] - poff[q]);
+    }
     drain.disarm();
     s = stagedev::read_errors(p, kHostErrWord, st);
     if (s != MSV_OK && s != MSV_ERR_BAD_RESIDUE && s != MSV_ERR_SEQUENCE_TOO_LONG) return s;
     return give(s);
+}
+
+}  // namespace
+
+extern "C" {
+
+msv_status msv_aln_align_batch_opts(msv_dom_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                                    const msv_aln_item* items, uint64_t m, const msv_aln_options* options,
+                                    msv_aln_result** result) {
+    msv_aln_options o;
+    std::memset(&o, 0, sizeof(o));
+    if (options) {
+        if (options->struct_size < sizeof(uint64_t)) return MSV_ERR_INVALID_ARGUMENT;
+        std::memcpy(&o, options, static_cast<size_t>(std::min<uint64_t>(options->struct_size, sizeof(o))));
+    }
+    return align_batch(p, residues, offsets, n, items, m, o.workspace_bytes, o.keep_posteriors, o.null2 != 0, result);
+}
+
+msv_status msv_aln_align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                               const msv_aln_item* items, uint64_t m, uint64_t workspace_bytes, int keep_posteriors,
+                               msv_aln_result** result) {
+    msv_aln_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.struct_size = sizeof(o);
+    o.workspace_bytes = workspace_bytes;
+    o.keep_posteriors = keep_posteriors;
+    return msv_aln_align_batch_opts(p, residues, offsets, n, items, m, &o, result);
+}
+
+msv_status msv_aln_result_null2(const msv_aln_result* r, float* null2, float* domcorrection) {
+    if (!r || !r->has_null2) return MSV_ERR_INVALID_ARGUMENT;
+    if (null2) std::copy(r->null2.begin(), r->null2.end(), null2);
+    if (domcorrection) std::copy(r->domcorr.begin(), r->domcorr.end(), domcorrection);
+    return MSV_OK;
+}
+
+msv_status msv_aln_result_null2_stats(const msv_aln_result* r, msv_aln_null2_stats* out) {
+    if (!r || !out || !r->has_null2 || out->struct_size < sizeof(uint32_t)) return MSV_ERR_INVALID_ARGUMENT;
+    msv_aln_null2_stats st;
+    std::memset(&st, 0, sizeof(st));
+    st.row_block = static_cast<uint32_t>(msv_host::kNull2RowBlock);
+    st.null2_ms = r->null2_ms;
+    st.partial_ms = r->null2_partial_ms;
+    st.slab_bytes = r->slab_bytes;
+    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(st)));
+    st.struct_size = size;
+    std::memcpy(out, &st, size);
+    return MSV_OK;
 }
 
 uint64_t msv_aln_result_count(const msv_aln_result* r) { return r ? r->env.size() : 0; }
@@ -392,6 +522,17 @@ msv_status msv_aln_describe(const msv_dom_profile* p, msv_aln_info* out) {
     if (hipFuncGetAttributes(&fa, alnk::walk_fn()) == hipSuccess) {
         info.walk_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
         info.walk_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
+    }
+    info.null2_row_block = static_cast<uint32_t>(msv_host::kNull2RowBlock);
+    if (const alnk::Null2Variant* nv = alnk::null2_variant(v->S, v->isc)) {
+        if (hipFuncGetAttributes(&fa, nv->partial_fn) == hipSuccess) {
+            info.null2_partial_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
+            info.null2_partial_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
+        }
+        if (hipFuncGetAttributes(&fa, nv->finish_fn) == hipSuccess) {
+            info.null2_finish_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
+            info.null2_finish_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
+        }
     }
     const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(info)));
     info.struct_size = size;

@@ -19,16 +19,24 @@
 
 namespace msv_host {
 
-// Forward P-value of one score (msv.h, msv_fwd_pvalues): HMMER3's exponential tail over STATS LOCAL FORWARD.
-// nullsc and bits are msv_pvalue_of's (float, as p7_bg_NullOne); an empty sequence gives 1.
-FWD_HD inline double fwd_pvalue_of(float score, uint64_t L, float tau, float lambda) {
-    if (L == 0) return 1.0;
+// The three steps of a Forward P-value, each written once (the bias stage, null2_host.cpp, takes them apart to put
+// its correction between the null1 score and the bits).  nullsc and bits are msv_pvalue_of's (float, as
+// p7_bg_NullOne): the null1 score of a sequence of L >= 1 residues, the bit score of nats above it, and HMMER3's
+// exponential tail over STATS LOCAL FORWARD.
+FWD_HD inline float null1_score(uint64_t L) {
     const float p1 = static_cast<float>(L) / static_cast<float>(L + 1);
-    const float nullsc = static_cast<float>(static_cast<double>(L) * log(static_cast<double>(p1)) +
-                                            log(1.0 - static_cast<double>(p1)));
-    const float bits = (score - nullsc) / 0.69314718055994529f;
+    return static_cast<float>(static_cast<double>(L) * log(static_cast<double>(p1)) +
+                              log(1.0 - static_cast<double>(p1)));
+}
+FWD_HD inline float bits_of(float nats) { return nats / 0.69314718055994529f; }
+FWD_HD inline double tail_pvalue(float bits, float tau, float lambda) {
     if (bits < tau) return 1.0;
     return exp(-static_cast<double>(lambda) * (static_cast<double>(bits) - static_cast<double>(tau)));
+}
+// Forward P-value of one score (msv.h, msv_fwd_pvalues); an empty sequence gives 1.
+FWD_HD inline double fwd_pvalue_of(float score, uint64_t L, float tau, float lambda) {
+    if (L == 0) return 1.0;
+    return tail_pvalue(bits_of(score - null1_score(L)), tau, lambda);
 }
 
 // The model of msv.h's Forward block as float64 odds: x = exp((double)score), -inf -> 0.

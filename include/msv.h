@@ -532,8 +532,8 @@ msv_status msv_vit_traces_stats(const msv_vit_traces* traces, msv_vit_trace_stat
  * may differ within the tolerance.
  * P-value (HMMER3): bits = (score - nullsc) / ln 2 with msv_pvalues' null1 nullsc; P = 1 when bits < tau,
  * else exp(-lambda (bits - tau)); tau, lambda = STATS LOCAL FORWARD (msv_hmm_stats slots 4 and 5).  The
- * null2 / bias corrections are not part of this stage; Backward, posterior decoding and domain envelopes are
- * the domain stage's (below). */
+ * null2 / bias corrections are the bias stage's (last block below); Backward, posterior decoding and domain
+ * envelopes are the domain stage's (below). */
 typedef struct msv_fwd_profile msv_fwd_profile;
 
 /* The serial float64 CPU Forward of one sequence, arguments as msv_vit_cpu_score.  L = 0 scores -inf; a code
@@ -639,7 +639,8 @@ msv_status msv_fwd_filter_batch(msv_profile* msv, msv_vit_profile* vit, msv_fwd_
  * occ[j] - end[j] < rt2, the region (start, j) is emitted, start unset, triggered cleared.  A region open
  * at L is not emitted.  Each region carries two serial float sums over its residues in index order:
  * expected_domains = sum begin, mass = sum occ.  Rescoring and aligning an envelope is the alignment stage's
- * (below); splitting a region with expected_domains well above 1 by stochastic clustering, and null2, are not done.
+ * (below), its null2 bias correction the bias stage's (last block); splitting a region with expected_domains well
+ * above 1 by stochastic clustering is not done.
  * The CPU function runs all this serially in float64 (odds rescaled by 2^256, as msv_fwd_cpu_score) and is
  * the reference of every test.  The device computes float32 odds rescaled by exact powers of two, Forward
  * and Backward each with its own running exponent; the exponents combine exactly, and for every residue
@@ -814,8 +815,9 @@ msv_status msv_dom_result_stats(const msv_dom_result* result, msv_dom_stats* out
  * msv_aln_cpu_align: |gpu - cpu| <= Le (posterior bound) + Le^2 2^-24 (a path sums Le posteriors, each within
  * the bound; Le float32 adds of partial sums <= Le).  The envelope score has Forward's bound; with Lc = Le it is
  * the Forward kernel's score of the same variant bit for bit.  Paths are compared exactly, and only against
- * msv_aln_oa on the device's own posteriors.  null2 / bias corrections and the stochastic clustering of regions
- * with expected_domains well above 1 are not part of this stage. */
+ * msv_aln_oa on the device's own posteriors.  The null2 bias correction of an envelope is the bias stage's (next
+ * block; the `null2` option of msv_aln_align_batch_opts); the stochastic clustering of regions with
+ * expected_domains well above 1 is not done. */
 typedef struct msv_aln_item {
     uint32_t seq;                  /* index of the parent sequence in the batch                     */
     uint32_t i_from, i_to;         /* 1-based first and last residue of the envelope                */
@@ -885,6 +887,10 @@ typedef struct msv_aln_info {
     uint32_t forward_lds_bytes, backward_lds_bytes, fill_lds_bytes, walk_lds_bytes;
     uint64_t default_workspace_bytes;
     char variant[64];
+    uint32_t null2_row_block;          /* R: rows of one unit of aln_null2_partial (bias stage)       */
+    uint32_t null2_partial_scratch_bytes, null2_finish_scratch_bytes;
+    uint32_t null2_partial_lds_bytes, null2_finish_lds_bytes;
+    uint32_t reserved;
 } msv_aln_info;
 msv_status msv_aln_describe(const msv_dom_profile* profile, msv_aln_info* out);
 
@@ -896,6 +902,97 @@ typedef struct msv_aln_stats {
     float forward_ms, backward_ms, fill_ms, walk_ms;
 } msv_aln_stats;
 msv_status msv_aln_result_stats(const msv_aln_result* result, msv_aln_stats* out);
+
+/* ---- Bias stage: the null2 model of an envelope and its corrected scores --------------------------
+ * The last step of HMMER3's rescore_isolated_domain: the null2 model of the envelope "by expectation" and the bias
+ * correction taken from it, which turns an envelope score into the per-domain bit score and P-value a search
+ * reports and, summed over a sequence's domains, into the per-sequence score that decides whether the hit is
+ * reported.  It removes the score that composition-biased and low-complexity sequences get from their composition.
+ * For an item (envelope) of Le residues and configured length Lc, with the posteriors of the alignment block,
+ * m[x][k] / ins[x][k] the FLOAT32 match / insert odds of residue x at node k (insert odds 1 in MSV_INSERTS_ZERO mode):
+ *   eM(k) = sum_i ppM(i,k), k = 1..LENG;   eI(k) = sum_i ppI(i,k), k = 1..LENG-1;   eX = sum_i (ppN(i) + ppJ(i) + ppC(i))
+ *   null2[x] = (1 / Le) (sum_k eM(k) m[x][k] + sum_k eI(k) ins[x][k] + eX)        x = 0..19  (N, J, C emit at odds 1)
+ * which is p7_GNull2_ByExpectation in probability space (the library accepts codes 0..19 only, so the degenerate
+ * symbols' averaging has nothing to do).  With n_x the count of x in the envelope:
+ *   domcorrection = sum_x n_x log(null2[x])   nats, terms with n_x = 0 skipped
+ *   omega = 1/256;   dombias = log(1 + omega exp(domcorrection))
+ *   domain bits = (envelope score + (Lc - Le) log loop(Lc) - nullsc(Lc) - dombias) / ln 2, nullsc msv_pvalues' null1;
+ *   the domain P-value is Forward's exponential tail on (tau, lambda), exactly as msv_fwd_pvalues computes it.
+ *   Per sequence: seqbias = log(1 + omega exp(sum of the domcorrection of its items)),
+ *   sequence bits = (Forward score - nullsc - seqbias) / ln 2, with its P-value.
+ * A model whose emission scores are all 0 has null2[x] = 1 up to rounding (rows sum to 1), so domcorrection = 0.
+ * If every match state gives residue a odds >= c > 1, insert odds are 1 and the envelope is made of a only, then
+ * null2[a] >= 1 + (c - 1) sum_k eM(k) / Le > 1: domcorrection > 0 and the corrected bits are below the uncorrected.
+ * msv_aln_cpu_null2 runs the float64 decode and the definition in float64 and is the reference of every tolerance.
+ * The device (aln_null2.hip) sums the float32 posteriors of the alignment workspace: a unit is (item, block of R =
+ * null2_row_block consecutive rows), one wave a unit adds its rows ascending into 2 S + 1 float32 sums per lane and
+ * writes a slab; one wave an item adds the slabs in block order, weights, sums across lanes in a fixed butterfly,
+ * adds eX and multiplies by 1 / Le.  The float32 order of summation is a function of (S, Le, R) only: a device
+ * null2 does not depend on the chunking, the item's place, the grid or the run.  An item whose envelope score is not
+ * finite is skipped: its null2 is zeros, its domcorrection 0.
+ * Tolerance (DESIGN 4.12 derives it; relative, because every term is non-negative).  With u = 2^-24,
+ *   W_x = sum_k m[x][k] + sum_k ins[x][k] + 3   (float64 sums of the float32 odds; ins = 1 for k = 1..LENG-1 without
+ *   insert scores) and, for every x,
+ *   delta_x = (48 (Le + LENG) + 2 (Le + 2 LENG + 8)) u null2_cpu[x] + W_x 2^-60
+ *   |null2_gpu[x] - null2_cpu[x]| <= delta_x
+ * (48 (Le + LENG) u: f, b and 1/Z each carry Forward's relative bound; 2 (Le + 2 LENG + 8) u: the float32 sums, the
+ * product, the scale and the roundings, for a variant with 2 S <= Le + 4 LENG + 7, which every variant the library
+ * picks satisfies; W_x 2^-60: cells that underflow float32 within a row's scale.  That last term is NOT derived: it
+ * ASSUMES that the Backward values of one row lie within 2^66 of the row's carrying cell, which the model's
+ * transition and emission ranges do not guarantee in general; the final rounding of a posterior alone accounts for
+ * W_x 2^-126 of it.  Everything else in the bound follows from the kernels as written.)  And, while delta_x <=
+ * null2_cpu[x] / 2 for every residue x that occurs in the item (a condition on the inputs),
+ *   |domcorrection_gpu - domcorrection_cpu| <= sum_x n_x delta_x / (null2_cpu[x] - delta_x)
+ *                                              + u (|domcorrection_cpu| + that sum) + 2^-149.
+ * The device's domcorrection is msv_aln_null2_correction on the device's own null2, bit for bit. */
+
+/* The float64 null2 of one envelope, model arguments as msv_aln_cpu_decode: null2 double [20], *domcorrection in nats;
+ * either may be NULL.  Le = 0 or Lc < Le gives MSV_ERR_INVALID_ARGUMENT, a code >= 20 MSV_ERR_BAD_RESIDUE. */
+msv_status msv_aln_cpu_null2(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                             uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                             uint64_t Le, uint64_t Lc, double* null2, double* domcorrection);
+/* THE definition of the correction from a float32 null2 vector: counts the residues, sums n_x log((double) null2[x])
+ * in float64 for x = 0..19 in that order (n_x = 0 skipped) and rounds once to float32. */
+msv_status msv_aln_null2_correction(const float* null2, const uint8_t* codes, uint64_t Le, float* domcorrection);
+/* The bias, bit score and P-value arithmetic above, on the host.  Per item q < m: envelope_scores, Le, Lc,
+ * domcorrection in; dombias, domain_bits (float), domain_pvalues (double) out.  Per sequence s < n_seq (n_seq may be
+ * 0: then nothing per sequence is read or written): parent[q] < n_seq names item q's sequence, fwd_scores and
+ * seq_lengths in; seq_bias, seq_bits, seq_pvalues out (a sequence with no item has seqbias log(1 + omega)).  Float
+ * where msv_fwd_pvalues is float, the sums of corrections and the logs in float64 rounded once.  Any output may be
+ * NULL. */
+msv_status msv_aln_bias_scores(const float* envelope_scores, const uint64_t* Le, const uint64_t* Lc,
+                               const float* domcorrection, uint64_t m, const uint32_t* parent, const float* fwd_scores,
+                               const uint64_t* seq_lengths, uint64_t n_seq, float tau, float lambda, float* dombias,
+                               float* domain_bits, double* domain_pvalues, float* seq_bias, float* seq_bits,
+                               double* seq_pvalues);
+
+/* Options of msv_aln_align_batch_opts.  Append-only: struct_size is set by the caller to sizeof(msv_aln_options);
+ * fields beyond it read as 0.  NULL options are all zeros. */
+typedef struct msv_aln_options {
+    uint64_t struct_size;
+    uint64_t workspace_bytes;  /* as msv_aln_align_batch's (0 = 1 GiB)                                       */
+    int32_t keep_posteriors;
+    int32_t null2;             /* run the bias stage's two launches per chunk (aln_null2.hip)                */
+} msv_aln_options;
+/* msv_aln_align_batch with options; msv_aln_align_batch is this call with null2 = 0.  With null2 = 0 no launch or
+ * allocation is added and every result byte is msv_aln_align_batch's.  With null2 the slabs of the partial sums live
+ * in a device buffer of the call's own, about 1 / null2_row_block of the matrix (never in the workspace: the chunk
+ * cuts are unchanged); if it cannot be allocated the call gives MSV_ERR_OUT_OF_MEMORY. */
+msv_status msv_aln_align_batch_opts(msv_dom_profile* profile, const uint8_t* residues, const uint64_t* offsets,
+                                    uint64_t n, const msv_aln_item* items, uint64_t n_items,
+                                    const msv_aln_options* options, msv_aln_result** result);
+/* null2 float [count][20] and domcorrection float [count] of a result made with the null2 option (else
+ * MSV_ERR_INVALID_ARGUMENT); either may be NULL. */
+msv_status msv_aln_result_null2(const msv_aln_result* result, float* null2, float* domcorrection);
+/* What the null2 launches did (msv_aln_stats has no size field and stays as it is): append-only as msv_aln_info. */
+typedef struct msv_aln_null2_stats {
+    uint32_t struct_size;
+    uint32_t row_block;        /* R                                                            */
+    float null2_ms;            /* summed device time of the two launches of every chunk       */
+    float partial_ms;          /* of it, the aln_null2_partial launches'                       */
+    uint64_t slab_bytes;       /* the slab buffer the call allocated                           */
+} msv_aln_null2_stats;
+msv_status msv_aln_result_null2_stats(const msv_aln_result* result, msv_aln_null2_stats* out);
 
 #ifdef __cplusplus
 } /* extern "C" */
