@@ -35,7 +35,7 @@ __all__ = [
     "encode", "sequence_transitions", "device_count", "score_grid", "score_grid_device", "score_batch_multi",
     "shard_bounds", "FASTA_device", "MultiGPU", "Viterbi_HMM", "filter_pipeline", "INSERTS_ZERO",
     "INSERTS_LOG_ODDS", "Traces", "Forward_HMM", "search_pipeline", "Domain_HMM", "Envelopes", "dom_regions",
-    "Alignments", "aln_oa",
+    "Alignments", "aln_oa", "Bias_filter", "background_frequencies",
 ]
 
 INSERTS_ZERO = 0      # HMMER3's insert scores (background emissions: 0)
@@ -166,6 +166,8 @@ class Profile_HMM:
         self.match_emissions = np.ctypeslib.as_array(L.msv_hmm_match_emissions(h), (M, 20)).copy()
         self.insert_emissions = np.ctypeslib.as_array(L.msv_hmm_insert_emissions(h), (M, 20)).copy()
         self.transitions = np.ctypeslib.as_array(L.msv_hmm_transitions(h), (M, 7)).copy()
+        # the COMPO line: the model's average composition (the bias filter's second state emits it)
+        self.compo = np.ctypeslib.as_array(L.msv_hmm_compo(h), (20,)).copy()
 
     def msv_scores(self) -> tuple[np.ndarray, float, float, float]:
         """MSV host precompute (MSV_HMM.cpp:35-57): ([20, M] log-odds, tr_B_Mk, tr_E_C, tr_E_J)."""
@@ -314,14 +316,20 @@ class MSV_HMM:
                                                pvalues_ptr, stream), "msv_pvalues_device")
 
     def msv_filter(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
-                   offsets: np.ndarray | None = None, F1: float = 0.02):
+                   offsets: np.ndarray | None = None, F1: float = 0.02, bias: "Bias_filter | None" = None):
         """Scores, P-values and the pass mask of HMMER3's MSV filter threshold (P <= F1, default
-        0.02 as hmmsearch's --F1)."""
+        0.02 as hmmsearch's --F1).  With bias=Bias_filter both of HMMER3's tests apply -- P <= F1 against null1,
+        then P <= F1 with the bias filter's score (msv.h "Bias filter") -- and the call returns (scores, filtered
+        P-values, mask, bias); the bias is 0 where the first test failed, so such a P-value is the null1 one."""
         if seqs is not None:
             codes, offsets = pack_sequences(seqs)
         sc = self.score_batch(codes=codes, offsets=offsets)
         pv = self.pvalues(sc, offsets)
-        return sc, pv, pv <= F1
+        if bias is None:
+            return sc, pv, pv <= F1
+        b = bias.score_batch(codes=codes, offsets=offsets, select=np.flatnonzero(pv <= F1))
+        fpv = bias.pvalues(sc, b, offsets, self.msv_mu, self.msv_lambda, kind="gumbel")
+        return sc, fpv, fpv <= F1, b
 
     def score_fasta_device(self, fasta: "FASTA_device") -> np.ndarray:
         """Scores of a GPU-parsed FASTA set (msv_score_fasta_device): no host parse, no H2D of residues."""
@@ -614,15 +622,46 @@ class Viterbi_HMM(_StageEngine):
         return _pvalues("msv_pvalues", scores, offsets, self.viterbi_mu, self.viterbi_lambda)
 
 
+def _sub_batch(codes: np.ndarray, offsets: np.ndarray, idx: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """The CSR batch of the sequences idx of a batch, in that order."""
+    lens = (offsets[1:] - offsets[:-1])[idx]
+    sub_off = np.zeros(len(idx) + 1, np.uint64)
+    np.cumsum(lens, out=sub_off[1:])
+    parts = [codes[int(offsets[i]):int(offsets[i + 1])] for i in idx]
+    return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), sub_off
+
+
+def _filter_pipeline_bias(msv_engine, vit_engine, bias_engine, codes, offsets, n, F1, align):
+    """filter_pipeline with the bias filter: HMMER3's two MSV-stage tests, Viterbi on the survivors of both (every
+    kernel scores a sequence independently of its batch, so the sub-batches give the cascade's own scores)."""
+    msc, _, mask, bias = msv_engine.msv_filter(codes=codes, offsets=offsets, F1=F1, bias=bias_engine)
+    idx = np.flatnonzero(mask)
+    vsc = np.full(n, -np.inf, np.float32)
+    vpv = np.full(n, np.nan)
+    if idx.size:
+        sub_codes, sub_off = _sub_batch(codes, offsets, idx)
+        vsc[idx] = vit_engine.score_batch(codes=sub_codes, offsets=sub_off)
+        vpv[idx] = bias_engine.pvalues(vsc, bias, offsets, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
+                                       kind="gumbel")[idx]
+    if align:
+        traces = vit_engine.trace_batch(codes=codes, offsets=offsets, select=idx.astype(np.uint32))
+        return msc, mask, vsc, vpv, bias, traces
+    return msc, mask, vsc, vpv, bias
+
+
 def filter_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, seqs: Sequence[str] | None = None, *,
                     codes: np.ndarray | None = None, offsets: np.ndarray | None = None, F1: float = 0.02,
-                    align: bool = False):
+                    align: bool = False, bias_engine: "Bias_filter | None" = None):
     """HMMER3's MSV -> Viterbi cascade on the GPU (msv_vit_filter_batch): MSV scores of every sequence,
     the survivors P <= F1 (STATS LOCAL MSV), their Viterbi scores (-inf elsewhere) and Viterbi P-values
     (STATS LOCAL VITERBI, NaN elsewhere).  Returns (msv_scores, passed, vit_scores, vit_pvalues); with
     align=True also the Traces of the sequences that passed, in index order (a second call that uploads the
-    batch again: Viterbi_HMM.trace_batch with select = the passed indices)."""
+    batch again: Viterbi_HMM.trace_batch with select = the passed indices).  With bias_engine (a Bias_filter) the
+    survivors also pass the filtered test (MSV_HMM.msv_filter(bias=)), the Viterbi P-values are the filtered ones
+    and the bias [n] is returned after vit_pvalues: (msv_scores, passed, vit_scores, vit_pvalues, bias[, traces])."""
     codes, offsets, n = _batch(seqs, codes, offsets)
+    if bias_engine is not None:
+        return _filter_pipeline_bias(msv_engine, vit_engine, bias_engine, codes, offsets, n, F1, align)
     msc = np.zeros(n, np.float32)
     passed = np.zeros(n, np.uint8)
     vsc = np.zeros(n, np.float32)
@@ -680,6 +719,130 @@ class Forward_HMM(_StageEngine):
         """Device P-values (float64 out) for device scores/offsets, async on `stream`."""
         check(_native.lib().msv_fwd_pvalues_device(self.device, scores_ptr, offsets_ptr, n, self.forward_tau,
                                                    self.forward_lambda, pvalues_ptr, stream), "msv_fwd_pvalues_device")
+
+
+def background_frequencies() -> np.ndarray:
+    """The 20 background frequencies every log-odds score of the library is taken against (float32)."""
+    return np.ctypeslib.as_array(_native.lib().msv_background_frequencies(), (20,)).copy()
+
+
+class Bias_filter:
+    """HMMER3's bias (composition) filter for one profile on one GPU (msv.h "Bias filter"): the Forward
+    score, in nats, of a two-state HMM -- background / the profile's COMPO composition -- over each sequence, which
+    replaces null1 in the P-values of the MSV, Viterbi and Forward filters.  Every score comes from the gfx950 kernel
+    (bias_filter.hip) except cpu_score, the float64 definition every test compares against.  `profile` is a
+    Profile_HMM, or a (compo[20], background[20], model_length) triple of raw arrays."""
+
+    def __init__(self, profile, device: int = 0):
+        L = _native.lib()
+        if isinstance(profile, Profile_HMM):
+            self.compo = np.ascontiguousarray(profile.compo, np.float32)
+            self.background = background_frequencies()
+            self.model_length = int(profile.model_length)
+            self._stats = {"msv": (profile.stats_local_msv_mu, profile.stats_local_msv_lambda),
+                           "viterbi": (profile.stats_local_viterbi_mu, profile.stats_local_viterbi_lambda),
+                           "forward": (profile.stats_local_forward_theta, profile.stats_local_forward_lambda)}
+        else:
+            self._stats = {}
+            compo, background, model_length = profile
+            self.compo = np.ascontiguousarray(compo, np.float32)
+            self.background = np.ascontiguousarray(background, np.float32)
+            self.model_length = int(model_length)
+        if self.compo.shape != (20,) or self.background.shape != (20,):
+            raise ValueError("compo and background are 20 values each")
+        p = C.c_void_p()
+        check(L.msv_bf_profile_create(device, self.compo.ctypes.data, self.background.ctypes.data, self.model_length,
+                                      C.byref(p)), "msv_bf_profile_create")
+        self._p = p
+        self.device = device
+
+    @staticmethod
+    def tolerance(lengths, cpu) -> np.ndarray:
+        """msv.h's bound on |device - cpu_score| for sequences of these lengths and float64 scores."""
+        L = np.asarray(lengths, np.float64)
+        k = 5.0 * L + 14.0 * np.ceil(L / 1024.0) + 4.0
+        u = 2.0 ** -24
+        return k * u / (1.0 - k * u) + u * np.abs(np.asarray(cpu, np.float64))
+
+    def cpu_score(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
+                  offsets: np.ndarray | None = None) -> np.ndarray:
+        """The float64 definition (msv_bf_cpu_score_batch) over a host batch -> float64 [n]."""
+        codes, offsets, n = _batch(seqs, codes, offsets)
+        out = np.zeros(n, np.float64)
+        _check_residues(_native.lib().msv_bf_cpu_score_batch(
+            self.compo.ctypes.data, self.background.ctypes.data, self.model_length, _ptr(codes), offsets.ctypes.data,
+            n, out.ctypes.data), "msv_bf_cpu_score_batch")
+        return out
+
+    def score_batch(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
+                    offsets: np.ndarray | None = None, select: np.ndarray | None = None) -> np.ndarray:
+        """The bias of every sequence of a host batch (msv_bf_score_batch, one launch) -> float32 [n].  With
+        `select` (indices) only those are scored, as a sub-batch; the others' entries are 0."""
+        codes, offsets, n = _batch(seqs, codes, offsets)
+        if select is not None:
+            idx = np.asarray(select, np.int64)
+            out = np.zeros(n, np.float32)
+            if idx.size:
+                sub_codes, sub_off = _sub_batch(codes, offsets, idx)
+                out[idx] = self.score_batch(codes=sub_codes, offsets=sub_off)
+            return out
+        out = np.zeros(n, np.float32)
+        _check_residues(_native.lib().msv_bf_score_batch(self._p, _ptr(codes), offsets.ctypes.data, n,
+                                                         out.ctypes.data, None), "msv_bf_score_batch")
+        return out
+
+    def score_batch_device(self, residues_ptr: int, residues_len: int, offsets_ptr: int, n: int, bias_ptr: int,
+                           select_ptr: int | None = None, select_count_ptr: int | None = None,
+                           stream: int | None = None) -> None:
+        """Device-resident batch (raw device pointers), optionally only the sequences listed at select_ptr
+        (uint32; their count in the device uint32 at select_count_ptr, else n); async on `stream`."""
+        check(_native.lib().msv_bf_score_batch_device(self._p, residues_ptr, residues_len, offsets_ptr, n, select_ptr,
+                                                      select_count_ptr, bias_ptr, stream),
+              "msv_bf_score_batch_device")
+
+    def pvalues(self, scores: np.ndarray, bias: np.ndarray, offsets: np.ndarray, location: float | None = None,
+                scale: float | None = None, *, kind: str = "msv") -> np.ndarray:
+        """Filtered P-values (msv_bf_pvalues) -> float64 [n].  kind "msv", "viterbi" (Gumbel) or "forward"
+        (exponential) takes the stage's STATS LOCAL line of the Profile_HMM this filter was made from; kind
+        "gumbel" with (location, scale) = (mu, lambda) or "exponential" with (tau, lambda) takes them as given."""
+        kinds = {"gumbel": _native.BF_GUMBEL, "exponential": _native.BF_EXPONENTIAL, "msv": _native.BF_GUMBEL,
+                 "viterbi": _native.BF_GUMBEL, "forward": _native.BF_EXPONENTIAL}
+        if kind not in kinds:
+            raise ValueError("kind is 'msv', 'viterbi', 'forward', 'gumbel' or 'exponential'")
+        if location is None or scale is None:
+            if kind not in self._stats:
+                raise ValueError(f"kind {kind!r} needs location and scale")
+            location, scale = self._stats[kind]
+        scores = np.ascontiguousarray(scores, np.float32)
+        bias = np.ascontiguousarray(bias, np.float32)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        if scores.shape != (n,) or bias.shape != (n,):
+            raise ValueError("scores, bias and offsets disagree")
+        out = np.zeros(n, np.float64)
+        check(_native.lib().msv_bf_pvalues(scores.ctypes.data, bias.ctypes.data, offsets.ctypes.data, n, location,
+                                           scale, kinds[kind], out.ctypes.data), "msv_bf_pvalues")
+        return out
+
+    def bind_stream(self, stream: int | None) -> None:
+        check(_native.lib().msv_bf_profile_bind_stream(self._p, stream), "msv_bf_profile_bind_stream")
+
+    def check(self, stream: int | None = None) -> None:
+        _check_residues(_native.lib().msv_bf_profile_check(self._p, stream), "msv_bf_profile_check")
+
+    def describe(self) -> dict:
+        info = _native.BfInfo()
+        check(_native.lib().msv_bf_profile_describe(self._p, C.byref(info)))
+        return info.as_dict()
+
+    def close(self):
+        lib = _loaded_lib()
+        if getattr(self, "_p", None) and lib is not None:
+            lib.msv_bf_profile_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
 
 
 class Envelopes:
@@ -1042,7 +1205,7 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
                     seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
                     offsets: np.ndarray | None = None, F1: float = 0.02, F2: float = 1e-3,
                     dom_engine: "Domain_HMM | None" = None, F3: float = 1e-5, align: bool = False,
-                    null2: bool = False) -> dict:
+                    null2: bool = False, bias_engine: "Bias_filter | None" = None) -> dict:
     """HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV over every sequence, P <= F1, Viterbi on the
     survivors, P <= F2, Forward on those, Forward P-values.  Returns the per-stage arrays: msv_scores, passed_msv,
     vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run).
@@ -1051,7 +1214,13 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
     needs dom_engine) also "alignments": Domain_HMM.align_batch of every region of those envelopes.  With null2=True
     (which needs align=True) the alignments carry null2 (msv.h "Bias stage") and the dict gains domain_bits,
     domain_pvalues (per alignment item) and seq_bias, seq_bits, seq_pvalues, indexed as the envelopes' sequences are
-    (entry q is sequence envelopes.select[q])."""
+    (entry q is sequence envelopes.select[q]).
+    With bias_engine (a Bias_filter: msv.h "Bias filter", HMMER3's composition filter, on by default in hmmsearch) the
+    call is msv_fwd_filter_batch_opts: the MSV survivors (passed_msv) are scored by the bias filter, only those whose
+    filtered MSV P-value is still <= F1 (passed_bias) reach Viterbi, the Viterbi and Forward tests and fwd_pvalues
+    use the filtered bit score, and the dict gains "bias" (float32 [n], 0 where not run) and "passed_bias"; the
+    dom_engine hit selection uses the filtered fwd_pvalues, as HMMER3's F3 test does; null2's reporting is against
+    null1 and null2, as HMMER3's, and does not change."""
     if null2 and not align:
         raise ValueError("null2=True needs align=True")
     codes, offsets, n = _batch(seqs, codes, offsets)
@@ -1061,12 +1230,23 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
     p1, p2 = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
     fpv = np.zeros(n, np.float64)
     n1, n2 = C.c_uint64(0), C.c_uint64(0)
-    _check_residues(_native.lib().msv_fwd_filter_batch(
-        msv_engine._p, vit_engine._p, fwd_engine._p, _ptr(codes), offsets.ctypes.data, n, stats.ctypes.data, F1, F2,
-        msc.ctypes.data, p1.ctypes.data, vsc.ctypes.data, p2.ctypes.data, fsc.ctypes.data, fpv.ctypes.data,
-        C.byref(n1), C.byref(n2)), "msv_fwd_filter_batch")
+    if bias_engine is None:
+        _check_residues(_native.lib().msv_fwd_filter_batch(
+            msv_engine._p, vit_engine._p, fwd_engine._p, _ptr(codes), offsets.ctypes.data, n, stats.ctypes.data, F1,
+            F2, msc.ctypes.data, p1.ctypes.data, vsc.ctypes.data, p2.ctypes.data, fsc.ctypes.data, fpv.ctypes.data,
+            C.byref(n1), C.byref(n2)), "msv_fwd_filter_batch")
+    else:
+        bias, pb, nb = np.zeros(n, np.float32), np.zeros(n, np.uint8), C.c_uint64(0)
+        opt = _native.SearchOptions(C.sizeof(_native.SearchOptions), 1, 0, bias_engine._p)
+        _check_residues(_native.lib().msv_fwd_filter_batch_opts(
+            msv_engine._p, vit_engine._p, fwd_engine._p, _ptr(codes), offsets.ctypes.data, n, stats.ctypes.data, F1,
+            F2, C.byref(opt), msc.ctypes.data, p1.ctypes.data, vsc.ctypes.data, p2.ctypes.data, fsc.ctypes.data,
+            fpv.ctypes.data, C.byref(n1), C.byref(n2), bias.ctypes.data, pb.ctypes.data, C.byref(nb)),
+            "msv_fwd_filter_batch_opts")
     out = {"msv_scores": msc, "passed_msv": p1.astype(bool), "vit_scores": vsc, "passed_vit": p2.astype(bool),
            "fwd_scores": fsc, "fwd_pvalues": fpv}
+    if bias_engine is not None:
+        out["bias"], out["passed_bias"] = bias, pb.astype(bool)
     if dom_engine is not None:
         hits = np.flatnonzero(p2.astype(bool) & (fpv <= F3)).astype(np.uint32)
         out["envelopes"] = dom_engine.decode_batch(codes=codes, offsets=offsets, select=hits)

@@ -75,7 +75,13 @@ EXPORTED = [
     "msv_aln_result_posteriors", "msv_aln_result_free", "msv_aln_describe", "msv_aln_result_stats",
     "msv_aln_cpu_null2", "msv_aln_null2_correction", "msv_aln_bias_scores", "msv_aln_align_batch_opts",
     "msv_aln_result_null2", "msv_aln_result_null2_stats",
+    "msv_hmm_compo", "msv_background_frequencies",
+    "msv_bf_cpu_score", "msv_bf_cpu_score_batch", "msv_bf_pvalues", "msv_bf_device_table", "msv_bf_profile_create",
+    "msv_bf_profile_create_from_hmm", "msv_bf_profile_destroy", "msv_bf_profile_describe", "msv_bf_score_batch",
+    "msv_bf_score_batch_device", "msv_bf_profile_bind_stream", "msv_bf_profile_check", "msv_bf_filter_select_device",
+    "msv_bf_pvalues_device", "msv_fwd_filter_batch_opts",
 ]
+BF_GUMBEL, BF_EXPONENTIAL = 0, 1  # msv.h MSV_BF_*: the tail of a filtered P-value
 
 
 class MSVError(RuntimeError):
@@ -305,6 +311,34 @@ class VitTraceStats(C.Structure):
                 ("walk_ms", C.c_float)]
 
 
+class BfInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("model_length", C.c_uint32),
+        ("residues_per_lane", C.c_uint32),
+        ("residues_per_trip", C.c_uint32),
+        ("waves_per_block", C.c_uint32),
+        ("blocks", C.c_uint32),
+        ("lds_bytes", C.c_uint32),
+        ("scratch_bytes", C.c_uint32),
+        ("vgprs", C.c_uint32),
+        ("device", C.c_int),
+        ("table", C.c_float * 26),
+        ("variant", C.c_char * 64),
+    ]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "struct_size"}
+        d["variant"] = self.variant.decode()
+        d["table"] = [float(x) for x in self.table]
+        return d
+
+
+class SearchOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint64), ("bias_filter", C.c_int32), ("reserved", C.c_int32),
+                ("bias_profile", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -490,6 +524,26 @@ def lib() -> C.CDLL:
         "msv_aln_align_batch_opts": (C.c_int, [vp, vp, vp, u64, vp, u64, C.POINTER(AlnOptions), C.POINTER(vp)]),
         "msv_aln_result_null2": (C.c_int, [vp, vp, vp]),
         "msv_aln_result_null2_stats": (C.c_int, [vp, C.POINTER(AlnNull2Stats)]),
+        "msv_hmm_compo": (fp, [vp]),
+        "msv_background_frequencies": (fp, []),
+        "msv_bf_cpu_score": (C.c_int, [vp, vp, u32, vp, u64, C.POINTER(C.c_double)]),
+        "msv_bf_cpu_score_batch": (C.c_int, [vp, vp, u32, vp, vp, u64, vp]),
+        "msv_bf_pvalues": (C.c_int, [vp, vp, vp, u64, f32, f32, C.c_int, vp]),
+        "msv_bf_device_table": (C.c_int, [vp, vp, u32, vp]),
+        "msv_bf_profile_create": (C.c_int, [C.c_int, vp, vp, u32, C.POINTER(vp)]),
+        "msv_bf_profile_create_from_hmm": (C.c_int, [C.c_int, vp, C.POINTER(vp)]),
+        "msv_bf_profile_destroy": (None, [vp]),
+        "msv_bf_profile_describe": (C.c_int, [vp, C.POINTER(BfInfo)]),
+        "msv_bf_score_batch": (C.c_int, [vp, vp, vp, u64, vp, vp]),
+        "msv_bf_score_batch_device": (C.c_int, [vp, vp, u64, vp, u64, vp, vp, vp, vp]),
+        "msv_bf_profile_bind_stream": (C.c_int, [vp, vp]),
+        "msv_bf_profile_check": (C.c_int, [vp, vp]),
+        "msv_bf_filter_select_device": (C.c_int, [C.c_int, vp, vp, vp, vp, u64, f32, f32, C.c_double, vp, vp, vp, vp]),
+        "msv_bf_pvalues_device": (C.c_int, [C.c_int, vp, vp, vp, u64, f32, f32, C.c_int, vp, vp]),
+        "msv_fwd_filter_batch_opts": (C.c_int, [vp, vp, vp, vp, vp, u64, vp, C.c_double, C.c_double,
+                                                C.POINTER(SearchOptions), vp, vp, vp, vp, vp, vp,
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp,
+                                                C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

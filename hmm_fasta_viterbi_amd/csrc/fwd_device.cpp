@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "bias_filter_device.h"
 #include "fwd_host.h"
 #include "fwd_kernel.h"
 #include "hip_rt.h"
@@ -186,9 +187,26 @@ msv_status msv_fwd_filter_batch(msv_profile* msv, msv_vit_profile* vit, msv_fwd_
                                 float* msv_scores, uint8_t* passed_msv, float* vit_scores, uint8_t* passed_vit,
                                 float* fwd_scores, double* fwd_pvalues, uint64_t* n_passed_msv,
                                 uint64_t* n_passed_vit) {
+    return msv_fwd_filter_batch_opts(msv, vit, fwd, residues, offsets, n, stats, F1, F2, nullptr, msv_scores,
+                                     passed_msv, vit_scores, passed_vit, fwd_scores, fwd_pvalues, n_passed_msv,
+                                     n_passed_vit, nullptr, nullptr, nullptr);
+}
+
+msv_status msv_fwd_filter_batch_opts(msv_profile* msv, msv_vit_profile* vit, msv_fwd_profile* fwd,
+                                     const uint8_t* residues, const uint64_t* offsets, uint64_t n, const float* stats,
+                                     double F1, double F2, const msv_search_options* options, float* msv_scores,
+                                     uint8_t* passed_msv, float* vit_scores, uint8_t* passed_vit, float* fwd_scores,
+                                     double* fwd_pvalues, uint64_t* n_passed_msv, uint64_t* n_passed_vit, float* bias,
+                                     uint8_t* passed_bias, uint64_t* n_passed_bias) {
     if (!msv || !vit || !fwd || !stats || !n_passed_msv || !n_passed_vit ||
         (n && (!offsets || !msv_scores || !passed_msv || !vit_scores || !passed_vit || !fwd_scores || !fwd_pvalues)))
         return MSV_ERR_INVALID_ARGUMENT;
+    msv_search_options opt{};  // fields beyond the caller's struct_size read as 0
+    if (options) std::memcpy(&opt, options, std::min<size_t>(sizeof(opt), options->struct_size));
+    msv_bf_profile* const bf = opt.bias_filter ? opt.bias_profile : nullptr;
+    if (opt.bias_filter && (!bf || !n_passed_bias || (n && (!bias || !passed_bias)) || bfdev::device_of(bf) != fwd->device))
+        return MSV_ERR_INVALID_ARGUMENT;
+    if (n_passed_bias) *n_passed_bias = 0;
     *n_passed_msv = *n_passed_vit = 0;
     if (n == 0) return MSV_OK;
     if (n >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
@@ -232,24 +250,51 @@ msv_status msv_fwd_filter_batch(msv_profile* msv, msv_vit_profile* vit, msv_fwd_
     if ((s = msv_filter_select_device(fwd->device, fwd->d_msv_out, sg.d_off, sg.d_order, n, stats[0], stats[1], F1,
                                       nullptr, fwd->d_sel1, d_n1, st)) != MSV_OK)
         return s;
-    if ((s = msv_vit_score_batch_device(vit, sg.d_res, total, sg.d_off, n, fwd->d_sel1, d_n1, fwd->d_vit_out, st)) !=
+    // with the bias filter (msv.h): the bias of those (0 elsewhere: such a sequence keeps its null1 P-value and
+    // stays out), then the filtered P <= F1 over every sequence in the same order gives Viterbi's list
+    const uint32_t* vit_sel = fwd->d_sel1;
+    const uint32_t* d_nvit = d_n1;
+    float* d_bias = nullptr;
+    uint32_t* d_selb = nullptr;
+    uint32_t* d_nb = nullptr;
+    if (bf) {
+        if ((s = bfdev::cascade_buffers(bf, n, &d_bias, &d_selb, &d_nb)) != MSV_OK) return s;
+        MSV_HIP(hipMemsetAsync(d_bias, 0, n * sizeof(float), st));
+        if ((s = msv_bf_score_batch_device(bf, sg.d_res, total, sg.d_off, n, fwd->d_sel1, d_n1, d_bias, st)) != MSV_OK)
+            return s;
+        if ((s = msv_bf_filter_select_device(fwd->device, fwd->d_msv_out, d_bias, sg.d_off, sg.d_order, n, stats[0],
+                                             stats[1], F1, nullptr, d_selb, d_nb, st)) != MSV_OK)
+            return s;
+        vit_sel = d_selb;
+        d_nvit = d_nb;
+    }
+    if ((s = msv_vit_score_batch_device(vit, sg.d_res, total, sg.d_off, n, vit_sel, d_nvit, fwd->d_vit_out, st)) !=
         MSV_OK)
         return s;
     // 4. P <= F2 over the Viterbi scores (a sequence that did not run has -inf, so P = 1); 5. Forward on them
     MSV_HIP(ninf_fill(sg.d_scores));
-    if ((s = msv_filter_select_device(fwd->device, fwd->d_vit_out, sg.d_off, sg.d_order, n, stats[2], stats[3], F2,
-                                      nullptr, fwd->d_sel2, d_n2, st)) != MSV_OK)
-        return s;
+    s = bf ? msv_bf_filter_select_device(fwd->device, fwd->d_vit_out, d_bias, sg.d_off, sg.d_order, n, stats[2],
+                                         stats[3], F2, nullptr, fwd->d_sel2, d_n2, st)
+           : msv_filter_select_device(fwd->device, fwd->d_vit_out, sg.d_off, sg.d_order, n, stats[2], stats[3], F2,
+                                      nullptr, fwd->d_sel2, d_n2, st);
+    if (s != MSV_OK) return s;
     if ((s = launch(fwd, sg.d_res, sg.d_off, n, fwd->d_sel2, d_n2, sg.d_scores, st, fwd->d_words + kHostErrWord)) !=
         MSV_OK)
         return s;
     // 6. Forward P-values (a sequence that did not run has -inf: bits < tau, P = 1)
-    MSV_HIP(fwdk::launch_fwd_pvalues(sg.d_scores, sg.d_off, n, stats[4], stats[5], fwd->d_pv, st));
+    // (with the bias filter they are taken on the host from the downloaded scores and bias, below: the outputs are
+    // host arrays, and fwd_pvalues is then msv_bf_pvalues on fwd_scores and bias to the last bit)
+    if (!bf) MSV_HIP(fwdk::launch_fwd_pvalues(sg.d_scores, sg.d_off, n, stats[4], stats[5], fwd->d_pv, st));
     uint32_t counts[2] = {0, 0};
+    uint32_t count_b = 0;
+    if (bf) {
+        MSV_HIP(hipMemcpyAsync(bias, d_bias, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        MSV_HIP(hipMemcpyAsync(&count_b, d_nb, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
     MSV_HIP(hipMemcpyAsync(msv_scores, fwd->d_msv_out, n * sizeof(float), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipMemcpyAsync(vit_scores, fwd->d_vit_out, n * sizeof(float), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipMemcpyAsync(fwd_scores, sg.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    MSV_HIP(hipMemcpyAsync(fwd_pvalues, fwd->d_pv, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (!bf) MSV_HIP(hipMemcpyAsync(fwd_pvalues, fwd->d_pv, n * sizeof(double), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipMemcpyAsync(counts, d_n1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipStreamSynchronize(st));
     drain.disarm();
@@ -257,11 +302,23 @@ msv_status msv_fwd_filter_batch(msv_profile* msv, msv_vit_profile* vit, msv_fwd_
     if ((s = stagedev::survivor_mask(st, counts[1], fwd->d_sel2, passed_vit, n)) != MSV_OK) return s;
     *n_passed_msv = counts[0];
     *n_passed_vit = counts[1];
+    if (bf) {
+        if ((s = msv_bf_pvalues(fwd_scores, bias, offsets, n, stats[4], stats[5], MSV_BF_EXPONENTIAL, fwd_pvalues)) !=
+            MSV_OK)
+            return s;
+        if ((s = stagedev::survivor_mask(st, count_b, d_selb, passed_bias, n)) != MSV_OK) return s;
+        *n_passed_bias = count_b;
+    } else {
+        if (bias) std::fill(bias, bias + n, 0.0f);
+        if (passed_bias) std::copy(passed_msv, passed_msv + n, passed_bias);
+        if (n_passed_bias) *n_passed_bias = counts[0];
+    }
     // every stage's word is read, so each call clears its own bits (a bad residue latches all three)
     s = msv_profile_check(msv, st);
     const msv_status vs = msv_vit_profile_check(vit, st);
     const msv_status fs = stagedev::read_errors(fwd, kHostErrWord, st);
-    return s != MSV_OK ? s : vs != MSV_OK ? vs : fs;
+    const msv_status bs = bf ? msv_bf_profile_check(bf, st) : MSV_OK;
+    return s != MSV_OK ? s : vs != MSV_OK ? vs : fs != MSV_OK ? fs : bs;
 }
 
 }  // extern "C"

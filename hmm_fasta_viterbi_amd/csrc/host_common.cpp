@@ -13,7 +13,17 @@
 #include "msv.h"
 #include "vit_trace_plan.h"
 
+namespace {
+// background_frequencies, MSV_HMM.cpp:21-27
+constexpr float kBackground[20] = {0.0787945f, 0.0151600f, 0.0535222f, 0.0668298f, 0.0397062f,
+                                   0.0695071f, 0.0229198f, 0.0590092f, 0.0594422f, 0.0963728f,
+                                   0.0237718f, 0.0414386f, 0.0482904f, 0.0395639f, 0.0540978f,
+                                   0.0683364f, 0.0540687f, 0.0673417f, 0.0114135f, 0.0304133f};
+}  // namespace
+
 extern "C" {
+
+const float* msv_background_frequencies(void) { return kBackground; }
 
 const char* msv_status_string(msv_status s) {
     switch (s) {
@@ -45,10 +55,7 @@ msv_status msv_hmm_msv_scores(const msv_hmm* hmm, float* emission_scores, float*
                               float* tr_E_J) {
     if (!hmm || !emission_scores || !tr_B_Mk || !tr_E_C || !tr_E_J) return MSV_ERR_INVALID_ARGUMENT;
     // MSV_HMM::MSV_HMM, MSV_HMM.cpp:35-57
-    static constexpr float bg[20] = {0.0787945f, 0.0151600f, 0.0535222f, 0.0668298f, 0.0397062f,
-                                     0.0695071f, 0.0229198f, 0.0590092f, 0.0594422f, 0.0963728f,
-                                     0.0237718f, 0.0414386f, 0.0482904f, 0.0395639f, 0.0540978f,
-                                     0.0683364f, 0.0540687f, 0.0673417f, 0.0114135f, 0.0304133f};
+    const float* const bg = kBackground;
     const size_t M = msv_hmm_model_length(hmm);
     const float* match = msv_hmm_match_emissions(hmm);
     for (size_t i = 0; i < M; ++i)

@@ -104,6 +104,13 @@ Probabilities_array<N> parse_probabilities(const char* c) {  // Profile_HMM.cpp:
     return r;
 }
 
+// Profile_HMM is filled here, in the library, inside an object the CALLER allocated: its layout is the reference's
+// and part of the binary interface.  A member added to it overruns the object of a caller built against an earlier
+// header (the COMPO values are therefore read apart, parse_compo, into the C handle).
+static_assert(sizeof(Profile_HMM) == sizeof(Profile_name) + 3 * sizeof(std::vector<float>) + sizeof(size_t) +
+                                         6 * sizeof(float),
+              "Profile_HMM has the reference's members only");
+
 msv_status parse_profile(const char* path, Profile_HMM& h) {
     std::string text;
     if (!read_file(path, text)) return MSV_ERR_IO;
@@ -163,6 +170,24 @@ msv_status parse_profile(const char* path, Profile_HMM& h) {
         h.transitions.push_back(parse_probabilities<NUM_OF_TRANSITIONS>(line.c_str()));
     }
     return MSV_OK;
+}
+
+// The 20 values of the COMPO line, exp(-value) as parse_profile parses every other row: the first line whose
+// left-stripped text starts with the tag, as value_after_tag finds it (the line sits in the file's header, so only
+// the head of the file is read).
+msv_status parse_compo(const char* path, Probabilities_array<NUM_OF_AMINO_ACIDS>& compo) {
+    std::ifstream in(path);
+    if (!in) return MSV_ERR_IO;
+    std::string line;
+    while (std::getline(in, line)) {
+        const char* c = line.c_str();
+        while (*c == ' ') ++c;
+        if (std::strncmp(c, "COMPO", 5) == 0) {
+            compo = parse_probabilities<NUM_OF_AMINO_ACIDS>(skip_word(c));
+            return MSV_OK;
+        }
+    }
+    return MSV_ERR_PARSE;
 }
 
 struct FastaData {
@@ -361,7 +386,10 @@ FASTA_protein_sequences::FASTA_protein_sequences(const std::string& file_path) {
 struct msv_hmm {
     Profile_HMM hmm;
     std::vector<float> match, insert, trans;  // flattened views
+    Probabilities_array<NUM_OF_AMINO_ACIDS> compo{};  // the COMPO line (not a member of Profile_HMM: see parse_profile)
     explicit msv_hmm(const char* path) : hmm(path) {
+        const msv_status cs = parse_compo(path, compo);
+        if (cs != MSV_OK) throw msv_error(cs, std::string(msv_status_string(cs)) + ": " + path);
         const size_t M = hmm.model_length;
         match.resize(M * 20);
         insert.resize(M * 20);
@@ -413,6 +441,7 @@ void msv_hmm_stats(const msv_hmm* hmm, float out6[6]) {
 const float* msv_hmm_match_emissions(const msv_hmm* hmm) { return hmm ? hmm->match.data() : nullptr; }
 const float* msv_hmm_insert_emissions(const msv_hmm* hmm) { return hmm ? hmm->insert.data() : nullptr; }
 const float* msv_hmm_transitions(const msv_hmm* hmm) { return hmm ? hmm->trans.data() : nullptr; }
+const float* msv_hmm_compo(const msv_hmm* hmm) { return hmm ? hmm->compo.data() : nullptr; }
 
 msv_status msv_fasta_read(const char* path, msv_fasta** out) {
     if (!path || !out) return MSV_ERR_INVALID_ARGUMENT;

@@ -68,6 +68,10 @@ void msv_hmm_stats(const msv_hmm* hmm, float out6[6]);
 const float* msv_hmm_match_emissions(const msv_hmm* hmm);
 const float* msv_hmm_insert_emissions(const msv_hmm* hmm);
 const float* msv_hmm_transitions(const msv_hmm* hmm);
+/* the COMPO line, the model's average match composition: 20 probabilities exp(-x), parsed as every other row */
+const float* msv_hmm_compo(const msv_hmm* hmm);
+/* the 20 background frequencies every log-odds score of the library is taken against (MSV_HMM.cpp:21-27) */
+const float* msv_background_frequencies(void);
 
 /* MSV host precompute -- replaces MSV_HMM::MSV_HMM (MSV_HMM.cpp:35-57).
  * emission_scores: caller buffer of 20 * model_length floats, residue-major,
@@ -993,6 +997,120 @@ typedef struct msv_aln_null2_stats {
     uint64_t slab_bytes;       /* the slab buffer the call allocated                           */
 } msv_aln_null2_stats;
 msv_status msv_aln_result_null2_stats(const msv_aln_result* result, msv_aln_null2_stats* out);
+
+/* ---- Bias filter: HMMER3's composition filter between MSV and Viterbi -----------------------------
+ * (Not the "bias stage" above: that is null2, per domain, at the end of the pipeline.  This is its per-sequence
+ * counterpart at the front, p7_bg_SetFilter / p7_bg_FilterScore, on by default in hmmsearch.)  A two-state HMM is
+ * run by Forward over the sequence: state 0 emits the background, state 1 the profile's average composition (the
+ * COMPO line).  Its score replaces null1 in the P-values of the MSV, Viterbi and Forward filters, so that a sequence
+ * that passes on composition alone does not reach the expensive stages.  The reference parses for this pipeline
+ * and never runs it: the model below is the definition, the float64 CPU twin (msv_bf_cpu_score) the reference of
+ * every tolerance, and parity with HMMER is unpinned, as for the Viterbi and Forward stages.
+ * For a profile with LENG = M (model_length = M + 1):
+ *   compo[x] = exp(-COMPO value), x = 0..19;   f[x] = msv_background_frequencies;   r[x] = compo[x] / f[x] in float64
+ *   states 0 (background, emission odds 1) and 1 (biased, emission odds r[x]);  L0 = 400, L1 = M / 8 as floats
+ *   t00 = L0/(L0+1)   t01 = 1/(L0+1)   t10 = 1/(L1+1)   t11 = L1/(L1+1)      pi0 = 0.999   pi1 = 0.001
+ *   both states go to the end with weight 1 (the length distribution is imposed outside).
+ * For residues x_1..x_L, with T = {t00 t01; t10 t11}:
+ *   v_1 = (pi0, pi1 r[x_1]);   v_i = (v_{i-1} T) diag(1, r[x_i]);   bias(seq) = log(v_L[0] + v_L[1]) nats;  0 for L = 0.
+ * HMMER's filtersc is nullsc + bias, nullsc msv_pvalues' null1, so the filtered bit score of any stage is
+ *   bits = (score - nullsc - bias) / ln 2
+ * through that stage's own tail: Gumbel (mu, lambda) for MSV and Viterbi, the exponential (tau, lambda) for Forward.
+ * A score of -inf gives P = 1 whatever the bias; with bias = 0 every formula is msv_pvalues' / msv_fwd_pvalues', bit
+ * for bit.
+ * The device (bias_filter.hip): one sequence per wave; the step is a 2x2 matrix product, so a trip of 1,024 residues
+ * -- counted from the sequence's first residue, never from its address -- is 64 lane products of 16 steps combined
+ * in lane order by a six-level cross-lane butterfly, all in float32, each product normalised by an exact power of
+ * two.  A bias is a function of the sequence and the profile alone.  L = 0 writes 0; a code >= 20 writes +inf and
+ * latches the bad-residue bit; a select entry >= n is latched and skipped; there is no length limit.
+ * Tolerance (DESIGN 4.13 counts the roundings; every term is non-negative, so the bound is relative in the odds and
+ * absolute in nats).  With u = 2^-24 and k = 5 L + 14 ceil(L / 1024) + 4, while k u < 1:
+ *   |bias_gpu - bias_cpu| <= k u / (1 - k u) + u |bias_cpu|
+ * The device needs 2^-24 <= r[x] <= 2^7 for every x (a composition and a background that are distributions give
+ * r <= 1 / min f < 88): msv_bf_profile_create gives MSV_ERR_UNSUPPORTED_MODEL otherwise. */
+typedef struct msv_bf_profile msv_bf_profile;
+enum { MSV_BF_GUMBEL = 0, MSV_BF_EXPONENTIAL = 1 }; /* the tail of a filtered P-value */
+
+/* THE definition, in float64, rescaled by exact powers of two: compo, background 20 floats each (compo finite and
+ * >= 0, background finite and > 0, else MSV_ERR_INVALID_ARGUMENT), model_length = LENG + 1 >= 2.  A code >= 20 gives
+ * MSV_ERR_BAD_RESIDUE.  The batch form runs it over CSR offsets. */
+msv_status msv_bf_cpu_score(const float* compo, const float* background, uint32_t model_length, const uint8_t* codes,
+                            uint64_t L, double* bias);
+msv_status msv_bf_cpu_score_batch(const float* compo, const float* background, uint32_t model_length,
+                                  const uint8_t* codes, const uint64_t* offsets, uint64_t n, double* bias);
+/* THE arithmetic of the filtered P-value, in float where msv_pvalues / msv_fwd_pvalues are float: their terms, with
+ * "- bias" after "- nullsc".  kind = MSV_BF_GUMBEL (location mu) or MSV_BF_EXPONENTIAL (location tau).  With bias
+ * all zero the results are those two calls', bitwise. */
+msv_status msv_bf_pvalues(const float* scores, const float* bias, const uint64_t* offsets, uint64_t n, float location,
+                          float scale, int kind, double* pvalues);
+/* The device table: 26 floats {t00, t01, t10, t11, pi0, pi1, r[0..19]}, each rounded once from float64. */
+msv_status msv_bf_device_table(const float* compo, const float* background, uint32_t model_length, float* table);
+
+msv_status msv_bf_profile_create(int device, const float* compo, const float* background, uint32_t model_length,
+                                 msv_bf_profile** out);
+msv_status msv_bf_profile_create_from_hmm(int device, const msv_hmm* hmm, msv_bf_profile** out);
+void msv_bf_profile_destroy(msv_bf_profile* profile);
+
+/* Append-only, as msv_aln_info: struct_size is written by the library. */
+typedef struct msv_bf_info {
+    uint32_t struct_size;
+    uint32_t model_length;
+    uint32_t residues_per_lane;  /* c: consecutive residues of a lane per trip */
+    uint32_t residues_per_trip;  /* 64 c                                       */
+    uint32_t waves_per_block;
+    uint32_t blocks;             /* persistent grid of a full launch           */
+    uint32_t lds_bytes;
+    uint32_t scratch_bytes;
+    uint32_t vgprs;
+    int device;
+    float table[26];             /* msv_bf_device_table                        */
+    char variant[64];
+} msv_bf_info;
+msv_status msv_bf_profile_describe(const msv_bf_profile* profile, msv_bf_info* out);
+
+/* The bias of every sequence of a host batch (one launch), and of a device-resident batch, optionally only the
+ * sequences listed at d_select (their count the device word d_select_count, else n), asynchronous on `stream`
+ * (NULL: the profile's own): conventions as msv_fwd_score_batch / msv_fwd_score_batch_device.  d_bias is written at
+ * the sequence's index; entries of sequences that are not listed are left as they were. */
+msv_status msv_bf_score_batch(msv_bf_profile* profile, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                              float* bias, void* stream);
+msv_status msv_bf_score_batch_device(msv_bf_profile* profile, const uint8_t* d_residues, uint64_t residues_len,
+                                     const uint64_t* d_offsets, uint64_t n, const uint32_t* d_select,
+                                     const uint32_t* d_select_count, float* d_bias, void* stream);
+msv_status msv_bf_profile_bind_stream(msv_bf_profile* profile, void* stream);
+msv_status msv_bf_profile_check(msv_bf_profile* profile, void* stream);
+/* msv_filter_select_device with the bias term: the same stable compaction in d_order, the same order contract;
+ * with d_bias all zero its list is msv_filter_select_device's. */
+msv_status msv_bf_filter_select_device(int device, const float* d_scores, const float* d_bias,
+                                       const uint64_t* d_offsets, const uint32_t* d_order, uint64_t n, float mu,
+                                       float lambda, double threshold, double* d_pvalues, uint32_t* d_selected,
+                                       uint32_t* d_count, void* stream);
+/* msv_bf_pvalues on the device (msv_pvalues_device / msv_fwd_pvalues_device with the bias term). */
+msv_status msv_bf_pvalues_device(int device, const float* d_scores, const float* d_bias, const uint64_t* d_offsets,
+                                 uint64_t n, float location, float scale, int kind, double* d_pvalues, void* stream);
+
+/* Options of msv_fwd_filter_batch_opts.  Append-only: struct_size is set by the caller to sizeof(msv_search_options);
+ * fields beyond it read as 0.  NULL options are all zeros. */
+typedef struct msv_search_options {
+    uint64_t struct_size;
+    int32_t bias_filter;          /* run the bias filter between MSV and Viterbi                     */
+    int32_t reserved;
+    msv_bf_profile* bias_profile; /* needed with bias_filter, on the cascade's device               */
+} msv_search_options;
+/* msv_fwd_filter_batch with options; msv_fwd_filter_batch is this call with NULL options, and with bias_filter = 0
+ * no launch or allocation is added and every output is that call's (bias, passed_bias, n_passed_bias may then be NULL;
+ * when given, bias is zeros and passed_bias is passed_msv).  With bias_filter, on one stream with no host round trip:
+ * MSV over all; P <= F1 on null1 gives list A (passed_msv); the bias of list A (0 elsewhere, which reproduces a
+ * sequence's null1 P-value exactly and keeps it out); filtered MSV P <= F1 gives list B (passed_bias), in the same
+ * longest-first order; Viterbi on B; filtered Viterbi P <= F2 gives list C (passed_vit); Forward on C; fwd_pvalues
+ * are the filtered ones (1 where Forward did not run), taken on the host after the download: msv_bf_pvalues on
+ * fwd_scores and bias, to the last bit. */
+msv_status msv_fwd_filter_batch_opts(msv_profile* msv, msv_vit_profile* vit, msv_fwd_profile* fwd,
+                                     const uint8_t* residues, const uint64_t* offsets, uint64_t n, const float* stats,
+                                     double F1, double F2, const msv_search_options* options, float* msv_scores,
+                                     uint8_t* passed_msv, float* vit_scores, uint8_t* passed_vit, float* fwd_scores,
+                                     double* fwd_pvalues, uint64_t* n_passed_msv, uint64_t* n_passed_vit, float* bias,
+                                     uint8_t* passed_bias, uint64_t* n_passed_bias);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -60,7 +60,24 @@ class Profile_HMM {
     float stats_local_msv_mu = 0, stats_local_msv_lambda = 0;
     float stats_local_viterbi_mu = 0, stats_local_viterbi_lambda = 0;
     float stats_local_forward_theta = 0, stats_local_forward_lambda = 0;
+    // (The reference's members and nothing else: the constructor lives in the library and fills the caller's
+    // object, so a member added here would overrun the object of every caller built against an earlier header.
+    // The COMPO line is profile_compo(), below.)
 };
+
+// The COMPO line of a profile file: the model's average match composition, exp(-value) as every other row (the
+// bias filter's second state emits it, msv.h "Bias filter").  It is not a member of Profile_HMM, whose layout is
+// the reference's; it is read from the file through the C-ABI (msv_hmm_read, msv_hmm_compo).
+inline Probabilities_array<NUM_OF_AMINO_ACIDS> profile_compo(const std::string& file_path) {
+    msv_hmm* h = nullptr;
+    const msv_status s = msv_hmm_read(file_path.c_str(), &h);
+    if (s != MSV_OK) throw msv_error(s, std::string(msv_status_string(s)) + ": " + file_path);
+    Probabilities_array<NUM_OF_AMINO_ACIDS> compo{};
+    const float* c = msv_hmm_compo(h);
+    for (int x = 0; x < NUM_OF_AMINO_ACIDS; ++x) compo[x] = c[x];
+    msv_hmm_destroy(h);
+    return compo;
+}
 
 // Residues packed for the device: codes 0..19 (255 = a symbol the scorer rejects), CSR offsets.
 struct Packed_sequences {
@@ -288,4 +305,69 @@ class Domain_HMM {
     std::vector<float> match_scores_, insert_scores_, transition_scores_;  // [20][M], [20][M], [M][7]
     float tr_B_Mk_ = 0, tr_E_C_ = 0, tr_E_J_ = 0;
     msv_dom_profile* profile_ = nullptr;
+};
+
+// The bias filter (msv.h "Bias filter"): HMMER3's composition filter, the Forward score of a two-state
+// HMM (background / the profile's COMPO composition) over each sequence, in nats.  Same surface as Forward_HMM:
+// run_on_sequence is the float64 CPU definition (msv_bf_cpu_score), the reference of every test;
+// parallel_run_on_sequence and score_batch the gfx950 kernel (float32, within msv.h's tolerance of it); pvalues are
+// the filtered P-values of a stage's scores (msv_bf_pvalues).  Header-only: every method is one C-ABI call.
+class Bias_filter {
+  public:
+    // compo: the profile's COMPO line (profile_compo(file_path)); the second form reads both from the file
+    Bias_filter(const Profile_HMM& base_hmm, const Probabilities_array<NUM_OF_AMINO_ACIDS>& compo, int device = 0)
+        : model_length_(base_hmm.model_length), compo_(compo) {
+        const msv_status s = msv_bf_profile_create(device, compo_.data(), msv_background_frequencies(),
+                                                   static_cast<uint32_t>(model_length_), &profile_);
+        if (s != MSV_OK) throw msv_error(s, std::string("msv_bf_profile_create: ") + msv_status_string(s));
+    }
+    explicit Bias_filter(const std::string& file_path, int device = 0)
+        : Bias_filter(Profile_HMM(file_path), profile_compo(file_path), device) {}
+    ~Bias_filter() { msv_bf_profile_destroy(profile_); }
+    Bias_filter(const Bias_filter&) = delete;
+    Bias_filter& operator=(const Bias_filter&) = delete;
+
+    double run_on_sequence(const Protein_sequence& seq) {
+        const Packed_sequences p = Packed_sequences::pack({seq});
+        double bias = 0;
+        check(msv_bf_cpu_score(compo_.data(), msv_background_frequencies(), static_cast<uint32_t>(model_length_),
+                               p.codes.data(), p.codes.size(), &bias),
+              "msv_bf_cpu_score");
+        return bias;
+    }
+    Log_score parallel_run_on_sequence(const Protein_sequence& seq) { return score_batch(Protein_sequences{seq})[0]; }
+    std::vector<Log_score> score_batch(const Protein_sequences& seqs) {
+        return score_batch(Packed_sequences::pack(seqs));
+    }
+    std::vector<Log_score> score_batch(const Packed_sequences& packed) {
+        std::vector<Log_score> out(packed.size());
+        check(msv_bf_score_batch(profile_, packed.codes.data(), packed.offsets.data(), packed.size(), out.data(),
+                                 nullptr),
+              "msv_bf_score_batch");
+        return out;
+    }
+    // kind: MSV_BF_GUMBEL with (mu, lambda), MSV_BF_EXPONENTIAL with (tau, lambda)
+    std::vector<double> pvalues(const std::vector<Log_score>& scores, const std::vector<Log_score>& bias,
+                                const Packed_sequences& packed, float location, float scale, int kind) const {
+        if (scores.size() != packed.size() || bias.size() != packed.size())
+            throw msv_error(MSV_ERR_INVALID_ARGUMENT, "scores, bias and sequences disagree");
+        std::vector<double> out(packed.size());
+        check(msv_bf_pvalues(scores.data(), bias.data(), packed.offsets.data(), packed.size(), location, scale, kind,
+                             out.data()),
+              "msv_bf_pvalues");
+        return out;
+    }
+
+    msv_bf_profile* handle() { return profile_; }
+    size_t model_length() const { return model_length_; }
+    const Probabilities_array<NUM_OF_AMINO_ACIDS>& compo() const { return compo_; }
+
+  private:
+    static void check(msv_status s, const char* what) {
+        if (s == MSV_ERR_BAD_RESIDUE) throw std::out_of_range("residue outside the 20 amino acids");
+        if (s != MSV_OK) throw msv_error(s, std::string(what) + ": " + msv_status_string(s));
+    }
+    size_t model_length_ = 0;
+    Probabilities_array<NUM_OF_AMINO_ACIDS> compo_{};
+    msv_bf_profile* profile_ = nullptr;
 };
