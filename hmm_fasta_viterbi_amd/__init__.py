@@ -35,7 +35,8 @@ __all__ = [
     "encode", "sequence_transitions", "device_count", "score_grid", "score_grid_device", "score_batch_multi",
     "shard_bounds", "FASTA_device", "MultiGPU", "Viterbi_HMM", "filter_pipeline", "INSERTS_ZERO",
     "INSERTS_LOG_ODDS", "Traces", "Forward_HMM", "search_pipeline", "Domain_HMM", "Envelopes", "dom_regions",
-    "Alignments", "aln_oa", "Bias_filter", "background_frequencies",
+    "Alignments", "aln_oa", "Bias_filter", "background_frequencies", "Ensembles", "dom_is_multidomain", "spl_cluster",
+    "spl_sample",
 ]
 
 INSERTS_ZERO = 0      # HMMER3's insert scores (background emissions: 0)
@@ -998,6 +999,139 @@ def aln_oa(ppM, ppI, ppN, ppJ, ppC, transition_scores, consts, Lc: int | None = 
     return np.float32(sc.value), doms, ops, pp
 
 
+def _items_of(items, envelopes, what: str) -> np.ndarray:
+    """The ITEM_DTYPE records of (seq, i_from, i_to) triples or records, or of every region of an Envelopes."""
+    if envelopes is not None:
+        if items is not None:
+            raise ValueError("give items or envelopes, not both")
+        reg = envelopes.regions
+        it = np.zeros(len(reg), _native.ITEM_DTYPE)
+        it["seq"], it["i_from"], it["i_to"] = reg["seq"], reg["i_from"], reg["i_to"]
+    elif items is None:
+        raise ValueError(f"{what} needs items or envelopes")
+    else:
+        src = np.asarray(items)
+        if src.dtype.names:
+            it = np.zeros(len(src), _native.ITEM_DTYPE)
+            for f in ("seq", "i_from", "i_to"):
+                it[f] = src[f]
+        else:
+            src = src.reshape(-1, 3)
+            if src.size and (src.min() < 0 or src.max() >= 2 ** 32):
+                raise ValueError("an item outside 32 bits")
+            it = np.zeros(len(src), _native.ITEM_DTYPE)
+            it["seq"], it["i_from"], it["i_to"] = src[:, 0], src[:, 1], src[:, 2]
+    return np.ascontiguousarray(it)
+
+
+def dom_is_multidomain(begin, end, i_from: int, i_to: int, rt3: float = 0.20) -> bool:
+    """HMMER3's is_multidomain_region (msv_dom_is_multidomain, THE definition) on the float32 begin / end arrays of
+    one sequence (residue i at index i - 1) for the region i_from .. i_to."""
+    b, e = (np.ascontiguousarray(x, np.float32) for x in (begin, end))
+    if not (b.shape == e.shape and b.ndim == 1):
+        raise ValueError("begin and end disagree")
+    out = C.c_int()
+    check(_native.lib().msv_dom_is_multidomain(_ptr(b), _ptr(e), b.size, int(i_from), int(i_to), rt3, C.byref(out)),
+          "msv_dom_is_multidomain")
+    return bool(out.value)
+
+
+def _cluster_options(min_overlap=0.8, max_diagdiff=4, min_posterior=0.25, min_endpointp=0.02):
+    """msv_spl_cluster_options: every fraction as the integer ratio the library tests with."""
+    from fractions import Fraction
+    o = _native.SplClusterOptions()
+    for name, x in (("min_overlap", min_overlap), ("min_posterior", min_posterior), ("min_endpointp", min_endpointp)):
+        f = Fraction(x).limit_denominator(10000)
+        if not 0 <= f <= 1:
+            raise ValueError(f"{name} outside [0, 1]")
+        setattr(o, name + "_num", f.numerator)
+        setattr(o, name + "_den", f.denominator)
+    if int(max_diagdiff) < 1:
+        raise ValueError("max_diagdiff must be at least 1")
+    o.max_diagdiff = int(max_diagdiff)
+    return o
+
+
+def spl_cluster(segments, n_samples: int, **options) -> np.ndarray:
+    """HMMER3's single-linkage clustering of sampled domains (msv_spl_cluster, THE definition) on the SEGMENT_DTYPE
+    records of one item's samples -> SPLIT_ENVELOPE_DTYPE records sorted by i_from.  Options: min_overlap=0.8,
+    max_diagdiff=4, min_posterior=0.25, min_endpointp=0.02."""
+    seg = np.ascontiguousarray(segments, _native.SEGMENT_DTYPE)
+    o = _cluster_options(**options)
+    L = _native.lib()
+    n = C.c_uint32()
+    check(L.msv_spl_cluster(_ptr(seg), len(seg), int(n_samples), C.byref(o), C.byref(n), None), "msv_spl_cluster")
+    out = np.zeros(n.value, _native.SPLIT_ENVELOPE_DTYPE)
+    if n.value:
+        check(L.msv_spl_cluster(_ptr(seg), len(seg), int(n_samples), C.byref(o), C.byref(n), out.ctypes.data),
+              "msv_spl_cluster")
+    return out
+
+
+def spl_sample(fM, fI, fD, records, transition_scores, consts, *, Lc: int, seq: int, i_from: int, i_to: int,
+               sample: int, seed: int = 42):
+    """THE definition of one stochastic traceback sample (msv_spl_sample) on the recorded planes of one envelope: fM,
+    fI, fD float32 [Le, LENG + 1], records uint32 [Le + 1, 6]; consts = (tr_B_Mk, tr_E_C, tr_E_J).  Returns
+    (segments with residues relative to the parent, domains and ops relative to the envelope, truncated)."""
+    pm, pi, pd = (np.ascontiguousarray(x, np.float32) for x in (fM, fI, fD))
+    rec = np.ascontiguousarray(records, np.uint32)
+    tsc = np.ascontiguousarray(transition_scores, np.float32)
+    Le, M = int(i_to) - int(i_from) + 1, tsc.shape[0]
+    if not (pm.shape == pi.shape == pd.shape == (Le, M) and rec.shape == (Le + 1, 6) and tsc.shape == (M, 7)):
+        raise ValueError("planes, records and transition scores disagree")
+    L = _native.lib()
+    ns, no, tr = C.c_uint32(), C.c_uint64(), C.c_int()
+    args = (_ptr(pm), _ptr(pi), _ptr(pd), _ptr(rec), tsc.ctypes.data, M, *[float(x) for x in consts], int(Lc),
+            int(seed), int(seq), int(i_from), int(i_to), int(sample))
+    check(L.msv_spl_sample(*args, C.byref(ns), C.byref(no), C.byref(tr), None, None, None), "msv_spl_sample")
+    segs = np.zeros(ns.value, _native.SEGMENT_DTYPE)
+    doms = np.zeros(ns.value, _native.DOMAIN_DTYPE)
+    ops = np.zeros(no.value, np.uint8)
+    if ns.value:
+        check(L.msv_spl_sample(*args, C.byref(ns), C.byref(no), C.byref(tr), segs.ctypes.data, doms.ctypes.data,
+                               ops.ctypes.data), "msv_spl_sample")
+    return segs, doms, ops, bool(tr.value)
+
+
+class Ensembles:
+    """What Domain_HMM.sample_batch returns, per item q in the caller's order (msv.h "Split stage"): `items`
+    (ITEM_DTYPE), envelope_scores[q] (nats), and the sampled domains as SEGMENT_DTYPE records (i_from, i_to relative
+    to the parent, k_from, k_to): sample j of item q owns segments[sample_offsets[q n_samples + j] :
+    sample_offsets[q n_samples + j + 1]].  `stats` says what the device did (truncated: samples that met a zero
+    total weight).  Made with keep_matrix=True, matrix(q) gives the recorded planes."""
+
+    def __init__(self, items, envelope_scores, sample_offsets, segments, n_samples, seed, *, status="MSV_OK",
+                 stats=None, matrices=None):
+        self.items, self.envelope_scores = items, envelope_scores
+        self.sample_offsets, self.segments = sample_offsets, segments
+        self.n_samples, self.seed = n_samples, seed
+        self.status = status
+        self.stats = stats or {}
+        self._matrices = matrices
+
+    def __len__(self) -> int:
+        return len(self.envelope_scores)
+
+    def segments_of(self, q: int, sample: int | None = None) -> np.ndarray:
+        """The segments of every sample of item q, or of one sample."""
+        lo = q * self.n_samples if sample is None else q * self.n_samples + sample
+        hi = (q + 1) * self.n_samples if sample is None else lo + 1
+        return self.segments[int(self.sample_offsets[lo]):int(self.sample_offsets[hi])]
+
+    def matrix(self, q: int):
+        """(fM, fI, fD, records) of item q as the device recorded them (keep_matrix=True): the planes float32
+        [Le, LENG + 1] in the scale of each row's exponent, records uint32 [Le + 1, 6]."""
+        if self._matrices is None:
+            raise ValueError("these ensembles were made without keep_matrix")
+        return self._matrices[q]
+
+    def cluster(self, q: int | None = None, **options):
+        """msv_spl_cluster on item q's segments -> SPLIT_ENVELOPE_DTYPE records; q None: a list, one per item."""
+        if q is None:
+            return [self.cluster(i, **options) for i in range(len(self))]
+        return spl_cluster(self.segments_of(q), self.n_samples, **options)
+
+
 def _domain_scores(envelope_scores, Le, Lc) -> np.ndarray:
     """envelope score + (Lc - Le) log(loop of Lc): HMMER's per-domain score, float32 adds on float32 values."""
     loops = np.array([sequence_transitions(int(x))[0] for x in Lc], np.float32)
@@ -1118,6 +1252,115 @@ class Domain_HMM(_StageEngine):
                                                          _ptr(pc)), "msv_aln_cpu_decode")
         return sc.value, pm, pi, pn, pj, pc
 
+    def split_describe(self) -> dict:
+        """msv_spl_describe: the split stage's variant, grid and, per kernel, scratch and LDS bytes."""
+        info = _native.SplInfo()
+        check(_native.lib().msv_spl_describe(self._p, C.byref(info)), "msv_spl_describe")
+        return info.as_dict()
+
+    def forward_on_envelope(self, seq=None, *, codes: np.ndarray | None = None, Lc: int | None = None):
+        """The float64 twin of the split stage's recording launch (msv_spl_cpu_forward) -> (score, fM, fI, fD
+        float64 [Le, LENG + 1], specials float64 [Le + 1, 5] = N, J, C, B, E, exponents int32 [Le + 1])."""
+        if seq is not None:
+            codes = encode(seq[1:] if seq.startswith("#") else seq)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        Le, M = codes.size, self.model_length
+        sc = C.c_double()
+        fm, fi, fd = (np.zeros((Le, M), np.float64) for _ in range(3))
+        sp, ex = np.zeros((Le + 1, 5), np.float64), np.zeros(Le + 1, np.int32)
+        _check_residues(_native.lib().msv_spl_cpu_forward(*self._tables(), _ptr(codes), Le, Le if Lc is None else Lc,
+                                                          C.byref(sc), _ptr(fm), _ptr(fi), _ptr(fd), _ptr(sp),
+                                                          _ptr(ex)), "msv_spl_cpu_forward")
+        return sc.value, fm, fi, fd, sp, ex
+
+    def sample_batch(self, seqs: Sequence[str] | None = None, items=None, *, codes: np.ndarray | None = None,
+                     offsets: np.ndarray | None = None, envelopes: "Envelopes | None" = None, n_samples: int = 200,
+                     seed: int = 42, workspace_bytes: int = 0, keep_matrix: bool = False, strict: bool = True,
+                     stream: int | None = None) -> Ensembles:
+        """Stochastic traceback ensembles of envelopes, on the GPU (msv_spl_sample_batch): per item a recording
+        Forward launch that keeps fM, fI and fD, then n_samples alignments sampled from the posterior, of which the
+        domains' end points are returned.  Items, envelopes=, workspace_bytes and strict as align_batch.  A sample's
+        random numbers are keyed by (seed, seq, i_from, i_to, sample), so an item's samples depend on nothing else."""
+        codes, offsets, n = _batch(seqs, codes, offsets)
+        it = _items_of(items, envelopes, "sample_batch")
+        L = _native.lib()
+        r = C.c_void_p()
+        opts = _native.SplOptions(workspace_bytes, seed, n_samples, 1 if keep_matrix else 0, stream)
+        st = L.msv_spl_sample_batch(self._p, _ptr(codes), offsets.ctypes.data, n, _ptr(it), len(it), C.byref(opts),
+                                    C.byref(r))
+        if not r.value:
+            check(st, "msv_spl_sample_batch")
+        try:
+            if st not in (_native.MSV_OK, _native.MSV_ERR_BAD_RESIDUE):
+                check(st, "msv_spl_sample_batch")
+            if strict:
+                _check_residues(st, "msv_spl_sample_batch")
+            m = L.msv_spl_result_count(r)
+            stats = _native.SplStats()
+            check(L.msv_spl_result_stats(r, C.byref(stats)))
+            ns = stats.n_samples
+            env = np.zeros(m, np.float32)
+            soff = np.zeros(m * ns + 1, np.uint64)
+            segs = np.zeros(L.msv_spl_result_segments(r), _native.SEGMENT_DTYPE)
+            check(L.msv_spl_result_copy(r, _ptr(env), soff.ctypes.data, _ptr(segs)), "msv_spl_result_copy")
+            mats = None
+            if keep_matrix:
+                mats = []
+                for q in range(m):
+                    Le = int(it["i_to"][q]) - int(it["i_from"][q]) + 1
+                    fm, fi, fd = (np.zeros((Le, self.model_length), np.float32) for _ in range(3))
+                    rec = np.zeros((Le + 1, 6), np.uint32)
+                    check(L.msv_spl_result_matrix(r, q, _ptr(fm), _ptr(fi), _ptr(fd), _ptr(rec)),
+                          "msv_spl_result_matrix")
+                    mats.append((fm, fi, fd, rec))
+            stats = {f: getattr(stats, f) for f, _ in stats._fields_ if f != "struct_size"}
+        finally:
+            L.msv_spl_result_free(r)
+        return Ensembles(it, env, soff, segs, ns, stats["seed"], status=_native.STATUS.get(st, str(st)), stats=stats,
+                         matrices=mats)
+
+    def split_regions(self, envelopes: "Envelopes", seqs: Sequence[str] | None = None, *,
+                      codes: np.ndarray | None = None, offsets: np.ndarray | None = None, rt3: float = 0.20,
+                      n_samples: int = 200, seed: int = 42, workspace_bytes: int = 0, **cluster_options) -> dict:
+        """HMMER3's treatment of multi-domain regions (msv.h "Split stage"): every region of `envelopes` is tested
+        with msv_dom_is_multidomain(rt3) on the entry's begin / end; the multi-domain ones are sampled on the GPU
+        (sample_batch) and clustered (msv_spl_cluster), and each is replaced by its clusters' envelopes (none if no
+        cluster passes).  Returns {"items": ITEM_DTYPE records for align_batch(items=), in region order; "region":
+        the index into envelopes.regions each item came from; "prob": float32, 1 for an unsplit region, else the
+        cluster's count / n_samples; "k_from", "k_to": the cluster's node range (0 for an unsplit region);
+        "multidomain": bool per region; "ensembles": the Ensembles of the multi-domain regions}."""
+        codes, offsets, n = _batch(seqs, codes, offsets)
+        reg = envelopes.regions
+        multi = np.zeros(len(reg), bool)
+        at = 0
+        for q in range(len(envelopes)):
+            b, e, _ = envelopes.posteriors(q)
+            for g in envelopes.regions_of(q):
+                multi[at] = dom_is_multidomain(b, e, int(g["i_from"]), int(g["i_to"]), rt3)
+                at += 1
+        idx = np.flatnonzero(multi)
+        sub = np.zeros(len(idx), _native.ITEM_DTYPE)
+        sub["seq"], sub["i_from"], sub["i_to"] = reg["seq"][idx], reg["i_from"][idx], reg["i_to"][idx]
+        ens = self.sample_batch(codes=codes, offsets=offsets, items=sub, n_samples=n_samples, seed=seed,
+                                workspace_bytes=workspace_bytes)
+        rows = []
+        where = {int(g): j for j, g in enumerate(idx)}
+        for g in range(len(reg)):
+            if not multi[g]:
+                rows.append((int(reg["seq"][g]), int(reg["i_from"][g]), int(reg["i_to"][g]), g, 1.0, 0, 0))
+                continue
+            for c in ens.cluster(where[g], **cluster_options):
+                rows.append((int(reg["seq"][g]), int(c["i_from"]), int(c["i_to"]), g, float(c["prob"]),
+                             int(c["k_from"]), int(c["k_to"])))
+        it = np.zeros(len(rows), _native.ITEM_DTYPE)
+        out = {"items": it, "region": np.zeros(len(rows), np.int64), "prob": np.zeros(len(rows), np.float32),
+               "k_from": np.zeros(len(rows), np.uint32), "k_to": np.zeros(len(rows), np.uint32),
+               "multidomain": multi, "ensembles": ens}
+        for j, (s, a, b, g, pr, kf, kt) in enumerate(rows):
+            it[j] = (s, a, b)
+            out["region"][j], out["prob"][j], out["k_from"][j], out["k_to"][j] = g, pr, kf, kt
+        return out
+
     def align_batch(self, seqs: Sequence[str] | None = None, items=None, *, codes: np.ndarray | None = None,
                     offsets: np.ndarray | None = None, envelopes: "Envelopes | None" = None,
                     workspace_bytes: int = 0, keep_posteriors: bool = False, strict: bool = True,
@@ -1130,27 +1373,7 @@ class Domain_HMM(_StageEngine):
         IndexError unless strict=False: then that item has no domains and `status` says so.  null2=True also runs the
         bias stage (msv.h "Bias stage"): the result carries `null2` and `domcorrection`, and bias_scores works."""
         codes, offsets, n = _batch(seqs, codes, offsets)
-        if envelopes is not None:
-            if items is not None:
-                raise ValueError("give items or envelopes, not both")
-            reg = envelopes.regions
-            it = np.zeros(len(reg), _native.ITEM_DTYPE)
-            it["seq"], it["i_from"], it["i_to"] = reg["seq"], reg["i_from"], reg["i_to"]
-        elif items is None:
-            raise ValueError("align_batch needs items or envelopes")
-        else:
-            src = np.asarray(items)
-            if src.dtype.names:
-                it = np.zeros(len(src), _native.ITEM_DTYPE)
-                for f in ("seq", "i_from", "i_to"):
-                    it[f] = src[f]
-            else:
-                src = src.reshape(-1, 3)
-                if src.size and (src.min() < 0 or src.max() >= 2 ** 32):
-                    raise ValueError("an item outside 32 bits")
-                it = np.zeros(len(src), _native.ITEM_DTYPE)
-                it["seq"], it["i_from"], it["i_to"] = src[:, 0], src[:, 1], src[:, 2]
-        it = np.ascontiguousarray(it)
+        it = _items_of(items, envelopes, "align_batch")
         L = _native.lib()
         r = C.c_void_p()
         opts = _native.AlnOptions(workspace_bytes, 1 if keep_posteriors else 0, 1 if null2 else 0)
@@ -1205,7 +1428,7 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
                     seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
                     offsets: np.ndarray | None = None, F1: float = 0.02, F2: float = 1e-3,
                     dom_engine: "Domain_HMM | None" = None, F3: float = 1e-5, align: bool = False,
-                    null2: bool = False, bias_engine: "Bias_filter | None" = None) -> dict:
+                    null2: bool = False, bias_engine: "Bias_filter | None" = None, split: bool = False) -> dict:
     """HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV over every sequence, P <= F1, Viterbi on the
     survivors, P <= F2, Forward on those, Forward P-values.  Returns the per-stage arrays: msv_scores, passed_msv,
     vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run).
@@ -1220,9 +1443,15 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
     filtered MSV P-value is still <= F1 (passed_bias) reach Viterbi, the Viterbi and Forward tests and fwd_pvalues
     use the filtered bit score, and the dict gains "bias" (float32 [n], 0 where not run) and "passed_bias"; the
     dom_engine hit selection uses the filtered fwd_pvalues, as HMMER3's F3 test does; null2's reporting is against
-    null1 and null2, as HMMER3's, and does not change."""
+    null1 and null2, as HMMER3's, and does not change.
+    With split=True (which needs align=True; msv.h "Split stage") the regions are first put through
+    Domain_HMM.split_regions: a multi-domain region is sampled and clustered, "alignments" holds one item per cluster
+    envelope in place of the region, and the dict gains "split" (split_regions' dict: which region each item came
+    from and its prob).  With split=False no launch or allocation is added and every returned byte is unchanged."""
     if null2 and not align:
         raise ValueError("null2=True needs align=True")
+    if split and not align:
+        raise ValueError("split=True needs align=True")
     codes, offsets, n = _batch(seqs, codes, offsets)
     stats = np.array([msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
                       fwd_engine.forward_tau, fwd_engine.forward_lambda], np.float32)
@@ -1251,8 +1480,13 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
         hits = np.flatnonzero(p2.astype(bool) & (fpv <= F3)).astype(np.uint32)
         out["envelopes"] = dom_engine.decode_batch(codes=codes, offsets=offsets, select=hits)
         if align:
-            out["alignments"] = dom_engine.align_batch(codes=codes, offsets=offsets, envelopes=out["envelopes"],
-                                                       null2=null2)
+            if split:
+                out["split"] = dom_engine.split_regions(out["envelopes"], codes=codes, offsets=offsets)
+                out["alignments"] = dom_engine.align_batch(codes=codes, offsets=offsets, items=out["split"]["items"],
+                                                           null2=null2)
+            else:
+                out["alignments"] = dom_engine.align_batch(codes=codes, offsets=offsets,
+                                                           envelopes=out["envelopes"], null2=null2)
             if null2:
                 b = out["alignments"].bias_scores(fwd_engine.forward_tau, fwd_engine.forward_lambda, fwd_scores=fsc)
                 out["domain_bits"], out["domain_pvalues"] = b["domain_bits"], b["domain_pvalues"]

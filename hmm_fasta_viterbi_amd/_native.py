@@ -80,6 +80,9 @@ EXPORTED = [
     "msv_bf_profile_create_from_hmm", "msv_bf_profile_destroy", "msv_bf_profile_describe", "msv_bf_score_batch",
     "msv_bf_score_batch_device", "msv_bf_profile_bind_stream", "msv_bf_profile_check", "msv_bf_filter_select_device",
     "msv_bf_pvalues_device", "msv_fwd_filter_batch_opts",
+    "msv_dom_is_multidomain", "msv_spl_cpu_forward", "msv_spl_sample", "msv_spl_cluster", "msv_spl_item_bytes",
+    "msv_spl_sample_batch", "msv_spl_result_count", "msv_spl_result_segments", "msv_spl_result_copy",
+    "msv_spl_result_matrix", "msv_spl_result_stats", "msv_spl_result_free", "msv_spl_describe",
 ]
 BF_GUMBEL, BF_EXPONENTIAL = 0, 1  # msv.h MSV_BF_*: the tail of a filtered P-value
 
@@ -261,6 +264,60 @@ class AlnNull2Stats(C.Structure):
         super().__init__()
         self.struct_size = C.sizeof(AlnNull2Stats)
 
+
+class SplOptions(C.Structure):
+    """msv_spl_options: append-only, struct_size first (set on construction)."""
+    _fields_ = [("struct_size", C.c_uint64), ("workspace_bytes", C.c_uint64), ("seed", C.c_uint64),
+                ("n_samples", C.c_uint32), ("seed_set", C.c_int32), ("keep_matrix", C.c_int32),
+                ("reserved", C.c_int32), ("stream", C.c_void_p)]
+
+    def __init__(self, workspace_bytes=0, seed=42, n_samples=200, keep_matrix=0, stream=None):
+        super().__init__(C.sizeof(SplOptions), workspace_bytes, seed, n_samples, 1, keep_matrix, 0, stream)
+
+
+class SplClusterOptions(C.Structure):
+    """msv_spl_cluster_options: append-only, struct_size first; fractions as integer ratios."""
+    _fields_ = [("struct_size", C.c_uint64), ("min_overlap_num", C.c_uint32), ("min_overlap_den", C.c_uint32),
+                ("max_diagdiff", C.c_uint32), ("min_posterior_num", C.c_uint32), ("min_posterior_den", C.c_uint32),
+                ("min_endpointp_num", C.c_uint32), ("min_endpointp_den", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(SplClusterOptions)
+
+
+class SplStats(C.Structure):
+    """msv_spl_stats: append-only, struct_size first (set before the call)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_samples", C.c_uint32), ("seed", C.c_uint64),
+                ("chunks", C.c_uint64), ("matrix_bytes", C.c_uint64), ("truncated", C.c_uint64),
+                ("forward_ms", C.c_float), ("sample_ms", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(SplStats)
+
+
+class SplInfo(C.Structure):
+    """msv_spl_info: append-only, struct_size first (set before the call)."""
+    _fields_ = [("struct_size", C.c_uint32), ("states_per_lane", C.c_uint32), ("forward_blocks", C.c_uint32),
+                ("forward_scratch_bytes", C.c_uint32), ("sample_scratch_bytes", C.c_uint32),
+                ("forward_lds_bytes", C.c_uint32), ("sample_lds_bytes", C.c_uint32), ("reserved", C.c_uint32),
+                ("default_workspace_bytes", C.c_uint64), ("variant", C.c_char * 64)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(SplInfo)
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f not in ("struct_size", "reserved")}
+        d["variant"] = self.variant.decode()
+        return d
+
+
+# msv_spl_segment and msv_spl_envelope as numpy structured dtypes
+SEGMENT_DTYPE = [("i_from", "<u4"), ("i_to", "<u4"), ("k_from", "<u4"), ("k_to", "<u4")]
+SPLIT_ENVELOPE_DTYPE = [("i_from", "<u4"), ("i_to", "<u4"), ("k_from", "<u4"), ("k_to", "<u4"), ("count", "<u4"),
+                        ("prob", "<f4")]
 
 # msv_aln_item as a numpy structured dtype
 ITEM_DTYPE = [("seq", "<u4"), ("i_from", "<u4"), ("i_to", "<u4")]
@@ -544,6 +601,21 @@ def lib() -> C.CDLL:
                                                 C.POINTER(SearchOptions), vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp,
                                                 C.POINTER(C.c_uint64)]),
+        "msv_dom_is_multidomain": (C.c_int, [vp, vp, u64, u32, u32, f32, C.POINTER(C.c_int)]),
+        "msv_spl_cpu_forward": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, u64, u64, C.POINTER(C.c_double),
+                                          vp, vp, vp, vp, vp]),
+        "msv_spl_sample": (C.c_int, [vp, vp, vp, vp, vp, u32, f32, f32, f32, u64, u64, u32, u32, u32, u32,
+                                     C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_int), vp, vp, vp]),
+        "msv_spl_cluster": (C.c_int, [vp, u64, u32, C.POINTER(SplClusterOptions), C.POINTER(u32), vp]),
+        "msv_spl_item_bytes": (u64, [u32, u64]),
+        "msv_spl_sample_batch": (C.c_int, [vp, vp, vp, u64, vp, u64, C.POINTER(SplOptions), C.POINTER(vp)]),
+        "msv_spl_result_count": (u64, [vp]),
+        "msv_spl_result_segments": (u64, [vp]),
+        "msv_spl_result_copy": (C.c_int, [vp, vp, vp, vp]),
+        "msv_spl_result_matrix": (C.c_int, [vp, u64, vp, vp, vp, vp]),
+        "msv_spl_result_stats": (C.c_int, [vp, C.POINTER(SplStats)]),
+        "msv_spl_result_free": (None, [vp]),
+        "msv_spl_describe": (C.c_int, [vp, C.POINTER(SplInfo)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

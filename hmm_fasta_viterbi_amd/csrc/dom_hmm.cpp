@@ -94,3 +94,70 @@ Envelopes Domain_HMM::decode_batch(const Packed_sequences& packed, const std::ve
     check(c, "msv_dom_result_copy");
     return e;
 }
+
+Split_regions Domain_HMM::split_regions(const Packed_sequences& packed, const Envelopes& e, float rt3,
+                                        uint32_t n_samples, uint64_t seed, uint64_t workspace_bytes) {
+    Split_regions out;
+    const size_t n_regions = e.regions.size();
+    out.multidomain.assign(n_regions, 0);
+    std::vector<msv_aln_item> multi;
+    for (size_t q = 0; q + 1 < e.region_offsets.size(); ++q) {
+        const uint64_t r0 = e.residue_offsets[q], L = e.residue_offsets[q + 1] - r0;
+        for (uint64_t g = e.region_offsets[q]; g < e.region_offsets[q + 1]; ++g) {
+            const msv_dom_region& r = e.regions[g];
+            int is_multi = 0;
+            check(msv_dom_is_multidomain(e.begin.data() + r0, e.end.data() + r0, L, r.i_from, r.i_to, rt3, &is_multi),
+                  "msv_dom_is_multidomain");
+            out.multidomain[g] = static_cast<uint8_t>(is_multi);
+            if (is_multi) multi.push_back(msv_aln_item{r.seq, r.i_from, r.i_to});
+        }
+    }
+    msv_spl_options opt{};
+    opt.struct_size = sizeof(opt);
+    opt.workspace_bytes = workspace_bytes;
+    opt.seed = seed;
+    opt.seed_set = 1;
+    opt.n_samples = n_samples;
+    msv_spl_result* r = nullptr;
+    const msv_status s = msv_spl_sample_batch(profile_, packed.codes.data(), packed.offsets.data(), packed.size(),
+                                              multi.data(), multi.size(), &opt, &r);
+    if (s == MSV_ERR_BAD_RESIDUE) {
+        msv_spl_result_free(r);
+        throw std::out_of_range("residue outside the 20 amino acids");
+    }
+    if (s != MSV_OK) msv_spl_result_free(r);
+    check(s, "msv_spl_sample_batch");
+    msv_spl_stats stats{};
+    stats.struct_size = sizeof(stats);
+    msv_status c = msv_spl_result_stats(r, &stats);
+    std::vector<msv_spl_segment> segs(msv_spl_result_segments(r));
+    std::vector<uint64_t> off(multi.size() * static_cast<size_t>(stats.n_samples) + 1, 0);
+    if (c == MSV_OK) c = msv_spl_result_copy(r, nullptr, off.data(), segs.data());
+    msv_spl_result_free(r);
+    check(c, "msv_spl_result_copy");
+    out.truncated = stats.truncated;
+    size_t at = 0;  // the next multi-domain region's place in `multi`
+    for (size_t g = 0; g < n_regions; ++g) {
+        const msv_dom_region& reg = e.regions[g];
+        if (!out.multidomain[g]) {
+            out.items.push_back(msv_aln_item{reg.seq, reg.i_from, reg.i_to});
+            out.region.push_back(g);
+            out.prob.push_back(1.0f);
+            continue;
+        }
+        const uint64_t lo = off[at * stats.n_samples], hi = off[(at + 1) * stats.n_samples];
+        ++at;
+        uint32_t n_env = 0;
+        check(msv_spl_cluster(segs.data() + lo, hi - lo, stats.n_samples, nullptr, &n_env, nullptr), "msv_spl_cluster");
+        std::vector<msv_spl_envelope> env(n_env);
+        if (n_env)
+            check(msv_spl_cluster(segs.data() + lo, hi - lo, stats.n_samples, nullptr, &n_env, env.data()),
+                  "msv_spl_cluster");
+        for (const msv_spl_envelope& c2 : env) {
+            out.items.push_back(msv_aln_item{reg.seq, c2.i_from, c2.i_to});
+            out.region.push_back(g);
+            out.prob.push_back(c2.prob);
+        }
+    }
+    return out;
+}

@@ -643,8 +643,8 @@ msv_status msv_fwd_filter_batch(msv_profile* msv, msv_vit_profile* vit, msv_fwd_
  * occ[j] - end[j] < rt2, the region (start, j) is emitted, start unset, triggered cleared.  A region open
  * at L is not emitted.  Each region carries two serial float sums over its residues in index order:
  * expected_domains = sum begin, mass = sum occ.  Rescoring and aligning an envelope is the alignment stage's
- * (below), its null2 bias correction the bias stage's (last block); splitting a region with expected_domains well
- * above 1 by stochastic clustering is not done.
+ * (below), its null2 bias correction the bias stage's; splitting a region that holds several domains by stochastic
+ * traceback clustering is the split stage's (last block).
  * The CPU function runs all this serially in float64 (odds rescaled by 2^256, as msv_fwd_cpu_score) and is
  * the reference of every test.  The device computes float32 odds rescaled by exact powers of two, Forward
  * and Backward each with its own running exponent; the exponents combine exactly, and for every residue
@@ -820,8 +820,8 @@ msv_status msv_dom_result_stats(const msv_dom_result* result, msv_dom_stats* out
  * the bound; Le float32 adds of partial sums <= Le).  The envelope score has Forward's bound; with Lc = Le it is
  * the Forward kernel's score of the same variant bit for bit.  Paths are compared exactly, and only against
  * msv_aln_oa on the device's own posteriors.  The null2 bias correction of an envelope is the bias stage's (next
- * block; the `null2` option of msv_aln_align_batch_opts); the stochastic clustering of regions with
- * expected_domains well above 1 is not done. */
+ * block; the `null2` option of msv_aln_align_batch_opts); the stochastic clustering of multi-domain regions is the
+ * split stage's (last block). */
 typedef struct msv_aln_item {
     uint32_t seq;                  /* index of the parent sequence in the batch                     */
     uint32_t i_from, i_to;         /* 1-based first and last residue of the envelope                */
@@ -1111,6 +1111,168 @@ msv_status msv_fwd_filter_batch_opts(msv_profile* msv, msv_vit_profile* vit, msv
                                      uint8_t* passed_msv, float* vit_scores, uint8_t* passed_vit, float* fwd_scores,
                                      double* fwd_pvalues, uint64_t* n_passed_msv, uint64_t* n_passed_vit, float* bias,
                                      uint8_t* passed_bias, uint64_t* n_passed_bias);
+
+/* ---- Split stage: stochastic traceback ensembles and the clustering of multi-domain regions ----
+ * A region that holds several tandem copies of a domain must not be rescored as one envelope.  This is the step of
+ * HMMER3's p7_domaindef_ByPosteriorHeuristics between the region rule and rescore_isolated_domain: a region is
+ * tested (is_multidomain_region), a multi-domain region has n_samples alignments sampled from the posterior by
+ * stochastic traceback over its Forward matrix, the sampled domains are clustered by their end points
+ * (p7_spensemble_Cluster) and each cluster's envelope is rescored by the alignment stage in place of the region.
+ * As for every stage since Viterbi, parity with HMMER is unpinned: the model is this header's (D_k -> E exits, no
+ * unihit reconfiguration for an envelope, as the alignment stage says), the random numbers are this block's.
+ *
+ * Which regions are split.  On the float32 begin / end arrays of msv_dom_decode_batch (residue i at index i - 1),
+ * for a region i_from .. i_to: Esum(z) = the serial float sum of end[i_from .. z] accumulated upward, Bsum(z) = the
+ * serial float sum of begin[z .. i_to] accumulated downward from i_to; the region is multi-domain iff
+ * max_z min(Esum(z), Bsum(z)) >= rt3 (HMMER's default 0.20).  Adds and compares only.
+ *
+ * The matrix.  An item is the alignment stage's (an envelope of Le residues decoded as a sequence of its own with
+ * the loop / move of the parent's length Lc).  A recording Forward launch (spl_kernel.hip: the Forward row of the
+ * Forward, domain and alignment stages, unchanged) stores for every row i = 1..Le the three planes fM, fI, fD as
+ * float32 in the scale of the row's exponent, next to the Le + 1 six-word records N, J, C, B, E, exponent of the
+ * domain stage: a stored value x of row i stands for x 2^exponent(i).  Every stored f carries Forward's relative
+ * bound 16 (Le + LENG) 2^-24 against msv_spl_cpu_forward (absolute 2^-126 in the row's scale where the float32
+ * value is subnormal or zero).
+ *
+ * The sampler (msv_spl_sample is THE definition; the device's spl_sample_kernel runs the same function,
+ * spl_host.h's spl_sample, one (item, sample) per thread, and reproduces it byte for byte on the same arrays).
+ * The walk starts in C(Le) and draws every source, options in this order, values as stored (float32), t the
+ * float32 odds of the device tables ((float) exp((double) score)), transitions indexed as in the Forward block:
+ *   C(i)   : C(i-1) loop | E(i) tEC                J(i) : J(i-1) loop | E(i) tEJ            B(i) : N(i) | J(i)
+ *   E(i)   : M(i,1), then for k = 2..LENG: M(i,k), D(i,k)
+ *   M(i,k) : M(i-1,k-1) tMM[k-1] | I(i-1,k-1) tIM[k-1] | D(i-1,k-1) tDM[k-1] | B(i-1) tBM
+ *   I(i,k) : M(i-1,k) tMI[k] | I(i-1,k) tII[k]     D(i,k) : M(i,k-1) tMD[k-1] | D(i,k-1) tDD[k-1]
+ * (row 0 and node 0 hold zeros and are not read).  In the two `loop` draws the older value is first moved to the
+ * newer row's scale by multiplications by powers of two (the recorded exponent difference; exact while the moved
+ * value is a normal float32, correctly rounded below that).  A draw: the
+ * weights w_j, each product rounded to float32 on its own; T = their float32 sum in index order; u = a 24-bit
+ * integer times 2^-24; t = u T (one rounding); the first j whose running prefix sum in the same order exceeds t;
+ * if none does, the last j with w_j > 0.  A weight of 0 is never picked.  T = 0 (every product underflowed) marks
+ * the sample truncated: it yields no further domain and is counted in the stats.  E's draw takes two passes over
+ * the row: the sum, then the pick.  No multiply feeds an add unrounded: the host object of this function is built
+ * with -ffp-contract=off as the device objects are.  Picking B from M(i,k) ends a domain (i_from = i, k_from = k;
+ * i_to and k_to are where E was left: k_to is the exit node, an M or a D); B(i) -> N ends the path, B(i) -> J
+ * continues with J(i).  Every step lowers i or k.
+ * Random numbers are counter-based, stateless and integer-only: with mix(x) the splitmix64 finaliser and
+ * g = 0x9e3779b97f4a7c15, h = seed, then h = mix(h + g + v) for v = the parent's sequence index, i_from, i_to (the
+ * envelope's, relative to the parent) and the sample index in turn; draw d = 0, 1, .. of the sample is
+ * mix(h + g (d + 1)) >> 40.  The key is the envelope's identity, so an item's samples do not depend on the batch,
+ * the item order, the chunking or the stream.  Defaults: seed 42, 200 samples (HMMER's).
+ *
+ * Clustering (msv_spl_cluster, host only): HMMER's single linkage on the segments (i_from, i_to, k_from, k_to) of
+ * all samples of one item.  Two segments are linked iff their residue ranges overlap by at least min_overlap of
+ * the shorter one, their node ranges likewise, |(i_from - k_from) - (i_from' - k_from')| <= max_diagdiff and the
+ * same for (i_to - k_to).  Fractions are integer ratios num / den and every test is in integers:
+ * den overlap >= num min(len, len'), with overlap = max(0, min(to, to') - max(from, from') + 1).  Clusters are the
+ * connected components, numbered by their lowest segment index; a cluster of `count` segments is kept iff
+ * den count >= num n_samples (min_posterior, 1/4).  Its i_from is the smallest value whose frequency f among the
+ * cluster's i_from has den f >= num count (min_endpointp, 1/50), its i_to the largest such value, k_from and k_to
+ * likewise (where no value reaches it, the smallest / largest value seen).  Envelopes come sorted by i_from (then
+ * cluster number), each with prob = count / n_samples (float).
+ * A multi-domain region is replaced by its clusters' envelopes, which may overlap; if no cluster passes, the
+ * region yields none. */
+typedef struct msv_spl_segment {
+    uint32_t i_from, i_to;         /* residues, 1-based, relative to the parent sequence */
+    uint32_t k_from, k_to;         /* nodes */
+} msv_spl_segment;
+typedef struct msv_spl_envelope {
+    uint32_t i_from, i_to, k_from, k_to;
+    uint32_t count;                /* segments of the cluster */
+    float prob;                    /* count / n_samples */
+} msv_spl_envelope;
+/* Append-only: struct_size is set by the caller; fields beyond it read as 0 and 0 means the default. */
+typedef struct msv_spl_cluster_options {
+    uint64_t struct_size;
+    uint32_t min_overlap_num, min_overlap_den;        /* 4 / 5  */
+    uint32_t max_diagdiff;                            /* 4 (UINT32_MAX: no limit; 0 is the default, not zero) */
+    uint32_t min_posterior_num, min_posterior_den;    /* 1 / 4  */
+    uint32_t min_endpointp_num, min_endpointp_den;    /* 1 / 50 */
+    uint32_t reserved;
+} msv_spl_cluster_options;
+typedef struct msv_spl_options {
+    uint64_t struct_size;
+    uint64_t workspace_bytes;      /* device workspace of a chunk (0 = 1 GiB)                              */
+    uint64_t seed;                 /* used as given when seed_set, else 42                                 */
+    uint32_t n_samples;            /* 0 = 200                                                              */
+    int32_t seed_set;
+    int32_t keep_matrix;           /* keep the recorded planes on the host for msv_spl_result_matrix       */
+    int32_t reserved;
+    void* stream;                  /* NULL: the profile's own                                              */
+} msv_spl_options;
+typedef struct msv_spl_result msv_spl_result;
+
+/* The region test above; *multidomain = 0 / 1.  i_from < 1, i_from > i_to or i_to > L: MSV_ERR_INVALID_ARGUMENT. */
+msv_status msv_dom_is_multidomain(const float* begin, const float* end, uint64_t L, uint32_t i_from, uint32_t i_to,
+                                  float rt3, int* multidomain);
+/* The float64 twin of the recording launch: the serial Forward of one envelope with D kept (rescaled by 2^256 as
+ * msv_dom_cpu_decode, model arguments as msv_aln_cpu_decode).  fM, fI, fD double [Le][LENG + 1] (row i - 1, column
+ * k; column 0 is 0), specials double [Le + 1][5] = N, J, C, B, E of rows 0..Le, exponents int32 [Le + 1]: a value x
+ * of row i stands for x 2^exponents[i].  *score = log Z.  Any output may be NULL. */
+msv_status msv_spl_cpu_forward(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                               uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                               uint64_t Le, uint64_t Lc, double* score, double* fM, double* fI, double* fD,
+                               double* specials, int32_t* exponents);
+/* THE definition of one sample, on arrays laid out as msv_spl_result_matrix returns them: fM, fI, fD float
+ * [Le][LENG + 1], records uint32 [Le + 1][6].  The sample's identity (seed, seq, i_from, i_to, sample) keys its
+ * random numbers; the envelope is residues i_from .. i_to of its parent (Le = i_to - i_from + 1) and segments carry
+ * residues relative to the parent.  Two calls size the output: with segments NULL only the counts are written; then
+ * segments[*n_segments], in residue order, and where ops is given the path as the Viterbi trace reports one:
+ * domains[*n_segments] (seq = 0, residues relative to the ENVELOPE, ops_begin from 0) and ops[*n_ops].
+ * *truncated = 1 if a draw met T = 0. */
+msv_status msv_spl_sample(const float* fM, const float* fI, const float* fD, const uint32_t* records,
+                          const float* transition_scores, uint32_t model_length, float tr_B_Mk, float tr_E_C,
+                          float tr_E_J, uint64_t Lc, uint64_t seed, uint32_t seq, uint32_t i_from, uint32_t i_to,
+                          uint32_t sample, uint32_t* n_segments, uint64_t* n_ops, int* truncated,
+                          msv_spl_segment* segments, msv_vit_domain* domains, uint8_t* ops);
+/* The clustering above on the n_segments segments of one item's n_samples samples, by the two-call protocol: with
+ * envelopes NULL only *n_envelopes is written.  NULL options are the defaults. */
+msv_status msv_spl_cluster(const msv_spl_segment* segments, uint64_t n_segments, uint32_t n_samples,
+                           const msv_spl_cluster_options* options, uint32_t* n_envelopes,
+                           msv_spl_envelope* envelopes);
+/* Workspace bytes of one item under a variant of S = states_per_lane: Le + 1 six-word records and Le rows of
+ * 3 S x 64 floats (fM, fI, fD by slot).  Chunks are cut by msv_vit_trace_chunk_cuts. */
+uint64_t msv_spl_item_bytes(uint32_t states_per_lane, uint64_t Le);
+
+/* Samples the items of a host batch on the device, synchronous: per chunk of items the recording launch, then the
+ * sampler's count pass, a host scan and its place pass.  Items, their checks, the workspace rule and the error
+ * classes are msv_aln_align_batch's; an item that was not decoded has no segments.  Results are per item in the
+ * caller's order, item q's sample j at entry q n_samples + j. */
+msv_status msv_spl_sample_batch(msv_dom_profile* profile, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                                const msv_aln_item* items, uint64_t n_items, const msv_spl_options* options,
+                                msv_spl_result** result);
+uint64_t msv_spl_result_count(const msv_spl_result* result);     /* items */
+uint64_t msv_spl_result_segments(const msv_spl_result* result);  /* segments in all */
+/* envelope_scores[count], sample_offsets[count n_samples + 1], segments[]; any may be NULL. */
+msv_status msv_spl_result_copy(const msv_spl_result* result, float* envelope_scores, uint64_t* sample_offsets,
+                               msv_spl_segment* segments);
+/* Item q's recorded planes as the device wrote them (keep_matrix, else MSV_ERR_INVALID_ARGUMENT), for tests: fM, fI,
+ * fD float [Le][LENG + 1], records uint32 [Le + 1][6]; any may be NULL.  An item that was not decoded has zeros. */
+msv_status msv_spl_result_matrix(const msv_spl_result* result, uint64_t q, float* fM, float* fI, float* fD,
+                                 uint32_t* records);
+/* Append-only, as msv_aln_null2_stats. */
+typedef struct msv_spl_stats {
+    uint32_t struct_size;
+    uint32_t n_samples;
+    uint64_t seed;
+    uint64_t chunks;
+    uint64_t matrix_bytes;         /* the recording launches wrote                  */
+    uint64_t truncated;            /* samples that met T = 0                        */
+    float forward_ms, sample_ms;   /* summed device times (HIP events); the sampler's two passes together */
+} msv_spl_stats;
+msv_status msv_spl_result_stats(const msv_spl_result* result, msv_spl_stats* out);
+void msv_spl_result_free(msv_spl_result* result);
+/* Append-only, as msv_aln_info. */
+typedef struct msv_spl_info {
+    uint32_t struct_size;
+    uint32_t states_per_lane;
+    uint32_t forward_blocks;
+    uint32_t forward_scratch_bytes, sample_scratch_bytes;
+    uint32_t forward_lds_bytes, sample_lds_bytes;
+    uint32_t reserved;
+    uint64_t default_workspace_bytes;
+    char variant[64];
+} msv_spl_info;
+msv_status msv_spl_describe(const msv_dom_profile* profile, msv_spl_info* out);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -284,6 +284,16 @@ struct Decoded_sequence {
     double forward_score = 0, backward_score = 0;
     std::vector<double> begin, end, occ;
 };
+// The split stage (msv.h "Split stage"): the items to align in place of the regions of an Envelopes.
+// A region that is not multi-domain is its own item (prob 1); a multi-domain region is replaced by its clusters'
+// envelopes (none if no cluster passes).  items[j] came from regions[region[j]].
+struct Split_regions {
+    std::vector<msv_aln_item> items;
+    std::vector<uint64_t> region;
+    std::vector<float> prob;
+    std::vector<uint8_t> multidomain;  // per region
+    uint64_t truncated = 0;            // samples that met a zero total weight
+};
 class Domain_HMM {
   public:
     explicit Domain_HMM(const Profile_HMM& base_hmm, int device = 0, msv_insert_mode inserts = MSV_INSERTS_ZERO);
@@ -295,6 +305,10 @@ class Domain_HMM {
     // select empty = every sequence; workspace_bytes 0 = the default (1 GiB)
     Envelopes decode_batch(const Packed_sequences& packed, const std::vector<uint32_t>& select = {},
                            float rt1 = 0.25f, float rt2 = 0.10f, uint64_t workspace_bytes = 0);
+    // HMMER3's treatment of multi-domain regions: msv_dom_is_multidomain(rt3) on every region of `envelopes` (made by
+    // decode_batch on `packed`), msv_spl_sample_batch on the multi-domain ones, msv_spl_cluster with its defaults
+    Split_regions split_regions(const Packed_sequences& packed, const Envelopes& envelopes, float rt3 = 0.20f,
+                                uint32_t n_samples = 200, uint64_t seed = 42, uint64_t workspace_bytes = 0);
 
     msv_dom_profile* handle() { return profile_; }
     size_t model_length() const { return model_length_; }
