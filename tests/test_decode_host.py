@@ -14,6 +14,7 @@ from hmm_fasta_viterbi_amd.synthetic import concat_batches, gapped_homolog_batch
 from decode_lib import cpu_decode, cpu_decode_batch, np_decode
 from forward_lib import DD, cpu_scores, tables
 from oracle_lib import PROFILES, ROOT, profile_path
+from sparse_lane_batches import SLOTS, sparse_lengths
 
 _hmm = {}
 
@@ -148,7 +149,12 @@ def test_rule_start_is_moved_forward_by_the_first_branch():
 
 # ---- scan constants, struct layout, sanitizers -------------------------------------------------------------------
 
-@pytest.mark.parametrize("leng,S", [(1, 2), (65, 2), (128, 2), (300, 6), (1400, 22), (1407, 22), (2432, 38)])
+SCAN_CASES = [(1, 2), (65, 2), (128, 2), (300, 6), (1400, 22), (1407, 22), (2432, 38)]
+# the sparse-lane lengths of every S, each once ((65, 2) is above already; 385 is two of S = 12's three)
+SCAN_CASES += [c for c in dict.fromkeys((leng, S) for S in SLOTS for leng in sparse_lengths(S)) if c not in SCAN_CASES]
+
+
+@pytest.mark.parametrize("leng,S", SCAN_CASES)
 def test_scan_constants_against_reversed_cumprod(leng, S):
     rng = np.random.Generator(np.random.PCG64(leng))
     M = leng + 1
@@ -169,6 +175,11 @@ def test_scan_constants_against_reversed_cumprod(leng, S):
     for j in range(6):
         want = np.array([np.prod(whole[l:min(64, l + 2 ** j)]) for l in range(64)])
         np.testing.assert_allclose(steps[j], want, rtol=2.0 ** -23, atol=1e-45)
+    # padding: the suffix product of every slot beyond LENG (and of node LENG, which has no d->d), and A_j[l] of every
+    # window l .. min(63, l + 2^j - 1) that reaches a padding lane (the lanes from LENG // S on), are exactly 0.0
+    assert not suffix.ravel()[leng - 1:].any()
+    for j in range(6 if leng < 64 * S else 0):
+        assert not steps[j, max(0, leng // S - 2 ** j + 1):].any(), j
     assert _native.lib().msv_dom_scan_constants(tsc.ctypes.data, M, 3, None, None, None) == 1  # odd S
     if leng > 128:
         assert _native.lib().msv_dom_scan_constants(tsc.ctypes.data, M, 2, None, None, None) == 1  # S too small

@@ -14,6 +14,7 @@ from hmm_fasta_viterbi_amd import _native
 from hmm_fasta_viterbi_amd.synthetic import (concat_batches, gapped_homolog_batch, homolog_batch, random_batch)
 from forward_lib import (DD, cpu_score, cpu_scores, distinct_exits, np_forward, stress_transitions, tables, tolerance)
 from oracle_lib import PROFILES, ROOT, profile_path
+from sparse_lane_batches import SLOTS, sparse_lengths
 
 _hmm = {}
 
@@ -228,7 +229,12 @@ def test_pvalues_against_a_float64_restatement():
     assert _native.lib().msv_fwd_pvalues(scores.ctypes.data, bad.ctypes.data, 2, tau, lam, out.ctypes.data) == 1
 
 
-@pytest.mark.parametrize("leng,S", [(1, 2), (65, 2), (128, 2), (300, 6), (1400, 22), (1407, 22), (2432, 38)])
+SCAN_CASES = [(1, 2), (65, 2), (128, 2), (300, 6), (1400, 22), (1407, 22), (2432, 38)]
+# the sparse-lane lengths of every S, each once ((65, 2) is above already; 385 is two of S = 12's three)
+SCAN_CASES += [c for c in dict.fromkeys((leng, S) for S in SLOTS for leng in sparse_lengths(S)) if c not in SCAN_CASES]
+
+
+@pytest.mark.parametrize("leng,S", SCAN_CASES)
 def test_scan_constants_against_cumprod(leng, S):
     rng = np.random.Generator(np.random.PCG64(leng))
     M = leng + 1
@@ -248,6 +254,9 @@ def test_scan_constants_against_cumprod(leng, S):
     for j in range(6):
         want = np.array([np.prod(whole[max(0, l - 2 ** j + 1):l + 1]) for l in range(64)])
         np.testing.assert_allclose(steps[j], want, rtol=2.0 ** -23, atol=1e-45)
+    # padding: the prefix product of every slot beyond LENG, and every step's multiplier of a lane whose window
+    # max(0, l - 2^j + 1) .. l holds a padding lane (lane l itself from LENG // S on), are exactly 0.0
+    assert not prefix.ravel()[leng:].any() and not steps[:, leng // S:].any()
     assert _native.lib().msv_fwd_scan_constants(tsc.ctypes.data, M, 3, None, None, None) == 1  # odd S
     if leng > 128:
         assert _native.lib().msv_fwd_scan_constants(tsc.ctypes.data, M, 2, None, None, None) == 1  # S too small

@@ -82,6 +82,56 @@ def test_describe_reports_the_row_block_and_no_scratch():
             assert old.null2_row_block == 0 and old.variant.decode() == p.info["variant"]
 
 
+def check_null2(p, model, codes, offsets, items, bad, refs, what):
+    """One device call with the posteriors kept on a list whose item `bad` holds a residue outside the 20; refs[q] =
+    (null2, domcorrection) of msv_aln_cpu_null2.  Every item within the bounds of the module docstring, its
+    domcorrection the definition on its own null2, its null2 the float64 sums over its own posteriors with the slots
+    beyond the model left out; returns the result."""
+    S, _ = shape_of(p.name)
+    M = model[0].shape[1]
+    leng = M - 1
+    off = offsets.astype(np.int64)
+    m32, i32 = odds32(model)
+    out = p.run(codes, offsets, items, status=4, keep=True)
+    assert out["null2"].shape == (len(items), 20) and out["null2_stats"]["row_block"] == R
+    units = sum(-(-(b - a + 1) // R) for _, a, b in items)
+    assert out["null2_stats"]["slab_bytes"] == units * (2 * S + 1) * 64 * 4 and out["stats"]["chunks"] == 1
+    worst_n2 = worst_dc = worst_sum = worst_rows = 0.0
+    for q, (s, a, b) in enumerate(items):
+        Le = b - a + 1
+        env = codes[off[s] + a - 1:off[s] + b]
+        got, got_dc = out["null2"][q], out["domcorr"][q]
+        if q == bad:
+            assert out["env"][q] == np.inf and not got.any() and got_dc == 0.0
+            continue
+        ref, ref_dc = refs[q]
+        delta = null2_bound(model, Le, ref)
+        err = np.abs(got.astype(np.float64) - ref)
+        worst_n2 = max(worst_n2, float(np.max(err / delta)))
+        tol = domcorr_bound(env, ref, delta, ref_dc)
+        worst_dc = max(worst_dc, abs(float(got_dc) - ref_dc) / tol)
+        # the definition on the device's own null2: bit for bit
+        st, want_dc = correction(got, env)
+        assert st == 0 and bits(np.array([got_dc])) == bits(np.array([want_dc])), (what, q, got_dc, want_dc)
+        # the masks at LENG and LENG - 1: float64 sums over the device's own posteriors, slots beyond the model
+        # left out, insert column LENG (which msv_aln_result_posteriors hands over as the device left it) too
+        pm, pi, pn, pj, pc = (x.astype(np.float64) for x in out["post"][q])
+        eM, eI = pm.sum(axis=0), pi.sum(axis=0)
+        eI[leng] = 0.0
+        eX = float((pn + pj + pc).sum())
+        total = eM.sum() + eI.sum() + eX
+        worst_rows = max(worst_rows, abs(total - Le) / (Le * leng * float(post_bound(Le, leng))))
+        own = (m32 @ eM + i32 @ eI + eX) / Le
+        own_tol = 2.0 * (Le + 2.0 * leng + 8.0) * U * own  # the sums, the product, the scale: no posterior error
+        worst_sum = max(worst_sum, float(np.max(np.abs(got.astype(np.float64) - own) / own_tol)))
+    print(f"{what}: {len(items)} items; worst null2 error {worst_n2:.4f} of its bound, worst domcorrection "
+          f"error {worst_dc:.4f} of its bound, null2 against float64 sums of the device's own posteriors "
+          f"{worst_sum:.4f} of the summation bound, |sum_k (eM + eI) + eX - Le| {worst_rows:.2e} of Le LENG x the "
+          f"posterior bound")
+    assert worst_n2 <= 1.0 and worst_dc <= 1.0 and worst_sum <= 1.0 and worst_rows <= 1.0, what
+    return out
+
+
 @pytest.mark.parametrize("name", VARIANTS)
 def test_null2_against_the_float64_twin(name):
     """LENG 64 S, 64 S - 1 and 64 (S - 2) + 1; null2_lib.null2_items: lane-edge homologs, envelopes of 1, 2, R - 1, R,
@@ -89,49 +139,10 @@ def test_null2_against_the_float64_twin(name):
     S, isc = shape_of(name)
     for which in range(3):
         model, codes, offsets, items, bad, refs = case(S, isc, which)
-        M = model[0].shape[1]
-        leng = M - 1
-        off = offsets.astype(np.int64)
+        leng = model[0].shape[1] - 1
         what = f"{name} LENG {leng}"
-        m32, i32 = odds32(model)
         with Profile(model, name) as p:
-            out = p.run(codes, offsets, items, status=4, keep=True)
-            assert out["null2"].shape == (len(items), 20) and out["null2_stats"]["row_block"] == R
-            units = sum(-(-(b - a + 1) // R) for _, a, b in items)
-            assert out["null2_stats"]["slab_bytes"] == units * (2 * S + 1) * 64 * 4 and out["stats"]["chunks"] == 1
-            worst_n2 = worst_dc = worst_sum = worst_rows = 0.0
-            for q, (s, a, b) in enumerate(items):
-                Le = b - a + 1
-                env = codes[off[s] + a - 1:off[s] + b]
-                got, got_dc = out["null2"][q], out["domcorr"][q]
-                if q == bad:
-                    assert out["env"][q] == np.inf and not got.any() and got_dc == 0.0
-                    continue
-                ref, ref_dc = refs[q]
-                delta = null2_bound(model, Le, ref)
-                err = np.abs(got.astype(np.float64) - ref)
-                worst_n2 = max(worst_n2, float(np.max(err / delta)))
-                tol = domcorr_bound(env, ref, delta, ref_dc)
-                worst_dc = max(worst_dc, abs(float(got_dc) - ref_dc) / tol)
-                # the definition on the device's own null2: bit for bit
-                st, want_dc = correction(got, env)
-                assert st == 0 and bits(np.array([got_dc])) == bits(np.array([want_dc])), (what, q, got_dc, want_dc)
-                # the masks at LENG and LENG - 1: float64 sums over the device's own posteriors, slots beyond the model
-                # left out, insert column LENG (which msv_aln_result_posteriors hands over as the device left it) too
-                pm, pi, pn, pj, pc = (x.astype(np.float64) for x in out["post"][q])
-                eM, eI = pm.sum(axis=0), pi.sum(axis=0)
-                eI[leng] = 0.0
-                eX = float((pn + pj + pc).sum())
-                total = eM.sum() + eI.sum() + eX
-                worst_rows = max(worst_rows, abs(total - Le) / (Le * leng * float(post_bound(Le, leng))))
-                own = (m32 @ eM + i32 @ eI + eX) / Le
-                own_tol = 2.0 * (Le + 2.0 * leng + 8.0) * U * own  # the sums, the product, the scale: no posterior error
-                worst_sum = max(worst_sum, float(np.max(np.abs(got.astype(np.float64) - own) / own_tol)))
-            print(f"{what}: {len(items)} items; worst null2 error {worst_n2:.4f} of its bound, worst domcorrection "
-                  f"error {worst_dc:.4f} of its bound, null2 against float64 sums of the device's own posteriors "
-                  f"{worst_sum:.4f} of the summation bound, |sum_k (eM + eI) + eX - Le| {worst_rows:.2e} of Le LENG x the "
-                  f"posterior bound")
-            assert worst_n2 <= 1.0 and worst_dc <= 1.0 and worst_sum <= 1.0 and worst_rows <= 1.0, what
+            out = check_null2(p, model, codes, offsets, items, bad, refs, what)
             # the repeated item has its original's bytes; without the bad item the others keep theirs (a second call)
             rep = len(items) - 2
             assert out["null2"][rep].tobytes() == out["null2"][0].tobytes()
