@@ -15,6 +15,8 @@ Python mirror of the reference's C++ class surface, bound to libmsv_hip.so (incl
     Domain_HMM(profile)                     (new, DESIGN 4.10: Backward, domain posteriors and envelopes of each hit;
                                              DESIGN 4.11: align_batch, the posterior decoding and optimal-accuracy
                                              alignment of each envelope)
+    calibrate(profile, msv, vit, fwd)       (new, DESIGN 4.15: the engines' own mu, tau and lambda, fitted on the GPU;
+                                             search_pipeline(..., stats=) takes them in place of the file's)
 
 Sequences use the reference's form ('#' sentinel + one-letter residues) or packed codes
 0..19 (alphabetical A C D E F G H I K L M N P Q R S T V W Y) with CSR offsets.
@@ -36,7 +38,8 @@ __all__ = [
     "shard_bounds", "FASTA_device", "MultiGPU", "Viterbi_HMM", "filter_pipeline", "INSERTS_ZERO",
     "INSERTS_LOG_ODDS", "Traces", "Forward_HMM", "search_pipeline", "Domain_HMM", "Envelopes", "dom_regions",
     "Alignments", "aln_oa", "Bias_filter", "background_frequencies", "Ensembles", "dom_is_multidomain", "spl_cluster",
-    "spl_sample",
+    "spl_sample", "Calibration", "calibrate", "cal_cpu_calibrate", "cal_lambda", "cal_thresholds",
+    "cal_codes_of_draws", "cal_generate", "cal_fit_location", "cal_fit_gumbel", "cal_tau", "write_hmm_stats",
 ]
 
 INSERTS_ZERO = 0      # HMMER3's insert scores (background emissions: 0)
@@ -317,19 +320,22 @@ class MSV_HMM:
                                                pvalues_ptr, stream), "msv_pvalues_device")
 
     def msv_filter(self, seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
-                   offsets: np.ndarray | None = None, F1: float = 0.02, bias: "Bias_filter | None" = None):
+                   offsets: np.ndarray | None = None, F1: float = 0.02, bias: "Bias_filter | None" = None,
+                   stats=None):
         """Scores, P-values and the pass mask of HMMER3's MSV filter threshold (P <= F1, default
         0.02 as hmmsearch's --F1).  With bias=Bias_filter both of HMMER3's tests apply -- P <= F1 against null1,
         then P <= F1 with the bias filter's score (msv.h "Bias filter") -- and the call returns (scores, filtered
-        P-values, mask, bias); the bias is 0 where the first test failed, so such a P-value is the null1 one."""
+        P-values, mask, bias); the bias is 0 where the first test failed, so such a P-value is the null1 one.
+        stats (a Calibration or six floats) replaces the file's STATS LOCAL MSV."""
         if seqs is not None:
             codes, offsets = pack_sequences(seqs)
+        mu, lam = (self.msv_mu, self.msv_lambda) if stats is None else _six_stats(stats)[:2]
         sc = self.score_batch(codes=codes, offsets=offsets)
-        pv = self.pvalues(sc, offsets)
+        pv = _pvalues("msv_pvalues", sc, offsets, mu, lam)
         if bias is None:
             return sc, pv, pv <= F1
         b = bias.score_batch(codes=codes, offsets=offsets, select=np.flatnonzero(pv <= F1))
-        fpv = bias.pvalues(sc, b, offsets, self.msv_mu, self.msv_lambda, kind="gumbel")
+        fpv = bias.pvalues(sc, b, offsets, mu, lam, kind="gumbel")
         return sc, fpv, fpv <= F1, b
 
     def score_fasta_device(self, fasta: "FASTA_device") -> np.ndarray:
@@ -632,18 +638,17 @@ def _sub_batch(codes: np.ndarray, offsets: np.ndarray, idx: np.ndarray) -> tuple
     return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), sub_off
 
 
-def _filter_pipeline_bias(msv_engine, vit_engine, bias_engine, codes, offsets, n, F1, align):
+def _filter_pipeline_bias(msv_engine, vit_engine, bias_engine, codes, offsets, n, F1, align, stats, six):
     """filter_pipeline with the bias filter: HMMER3's two MSV-stage tests, Viterbi on the survivors of both (every
     kernel scores a sequence independently of its batch, so the sub-batches give the cascade's own scores)."""
-    msc, _, mask, bias = msv_engine.msv_filter(codes=codes, offsets=offsets, F1=F1, bias=bias_engine)
+    msc, _, mask, bias = msv_engine.msv_filter(codes=codes, offsets=offsets, F1=F1, bias=bias_engine, stats=stats)
     idx = np.flatnonzero(mask)
     vsc = np.full(n, -np.inf, np.float32)
     vpv = np.full(n, np.nan)
     if idx.size:
         sub_codes, sub_off = _sub_batch(codes, offsets, idx)
         vsc[idx] = vit_engine.score_batch(codes=sub_codes, offsets=sub_off)
-        vpv[idx] = bias_engine.pvalues(vsc, bias, offsets, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
-                                       kind="gumbel")[idx]
+        vpv[idx] = bias_engine.pvalues(vsc, bias, offsets, six[2], six[3], kind="gumbel")[idx]
     if align:
         traces = vit_engine.trace_batch(codes=codes, offsets=offsets, select=idx.astype(np.uint32))
         return msc, mask, vsc, vpv, bias, traces
@@ -652,28 +657,32 @@ def _filter_pipeline_bias(msv_engine, vit_engine, bias_engine, codes, offsets, n
 
 def filter_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, seqs: Sequence[str] | None = None, *,
                     codes: np.ndarray | None = None, offsets: np.ndarray | None = None, F1: float = 0.02,
-                    align: bool = False, bias_engine: "Bias_filter | None" = None):
+                    align: bool = False, bias_engine: "Bias_filter | None" = None, stats=None):
     """HMMER3's MSV -> Viterbi cascade on the GPU (msv_vit_filter_batch): MSV scores of every sequence,
     the survivors P <= F1 (STATS LOCAL MSV), their Viterbi scores (-inf elsewhere) and Viterbi P-values
     (STATS LOCAL VITERBI, NaN elsewhere).  Returns (msv_scores, passed, vit_scores, vit_pvalues); with
     align=True also the Traces of the sequences that passed, in index order (a second call that uploads the
     batch again: Viterbi_HMM.trace_batch with select = the passed indices).  With bias_engine (a Bias_filter) the
     survivors also pass the filtered test (MSV_HMM.msv_filter(bias=)), the Viterbi P-values are the filtered ones
-    and the bias [n] is returned after vit_pvalues: (msv_scores, passed, vit_scores, vit_pvalues, bias[, traces])."""
+    and the bias [n] is returned after vit_pvalues: (msv_scores, passed, vit_scores, vit_pvalues, bias[, traces]).
+    stats (a Calibration, e.g. calibrate()'s, or six floats in msv_hmm_stats' order) replaces the engines' file
+    values in every test and P-value; with stats=None nothing changes."""
     codes, offsets, n = _batch(seqs, codes, offsets)
+    six = (msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda, 0.0, 0.0) \
+        if stats is None else _six_stats(stats)
     if bias_engine is not None:
-        return _filter_pipeline_bias(msv_engine, vit_engine, bias_engine, codes, offsets, n, F1, align)
+        return _filter_pipeline_bias(msv_engine, vit_engine, bias_engine, codes, offsets, n, F1, align, stats, six)
     msc = np.zeros(n, np.float32)
     passed = np.zeros(n, np.uint8)
     vsc = np.zeros(n, np.float32)
     npass = C.c_uint64(0)
     _check_residues(_native.lib().msv_vit_filter_batch(
-        msv_engine._p, vit_engine._p, _ptr(codes), offsets.ctypes.data, n, msv_engine.msv_mu, msv_engine.msv_lambda,
+        msv_engine._p, vit_engine._p, _ptr(codes), offsets.ctypes.data, n, six[0], six[1],
         F1, msc.ctypes.data, passed.ctypes.data, vsc.ctypes.data, C.byref(npass)), "msv_vit_filter_batch")
     mask = passed.astype(bool)
     vpv = np.full(n, np.nan)
     if mask.any():
-        vpv[mask] = vit_engine.pvalues(vsc, offsets)[mask]
+        vpv[mask] = _pvalues("msv_pvalues", vsc, offsets, six[2], six[3])[mask]
     if align:
         traces = vit_engine.trace_batch(codes=codes, offsets=offsets, select=np.flatnonzero(mask).astype(np.uint32))
         return msc, mask, vsc, vpv, traces
@@ -1424,11 +1433,188 @@ class Domain_HMM(_StageEngine):
                           domcorrection=dc, parent_lengths=lengths)
 
 
+class Calibration:
+    """What calibrate() returns (msv.h "Calibration"): `stats`, float32[6] in msv_hmm_stats' order (MSV
+    mu, lambda, Viterbi mu, lambda, Forward tau, lambda) -- the slots of an engine that was not given hold the file's
+    values; `lambda_`, the profile's lambda in float64; `report`, the float64 values, the fitted Gumbel, the Newton
+    iterations and the chunk counts; `from_file`, the file's own six for comparison; `scores`, per set that ran the
+    sample's raw scores when they were asked for.  Pass it as `stats=` to filter_pipeline / search_pipeline."""
+
+    def __init__(self, stats, lambda_, report, from_file, scores=None):
+        self.stats = np.asarray(stats, np.float32)
+        self.lambda_ = float(lambda_)
+        self.report = report
+        self.from_file = np.asarray(from_file, np.float32)
+        self.scores = scores or {}
+
+    def __repr__(self):
+        return f"Calibration(stats={self.stats.tolist()}, from_file={self.from_file.tolist()})"
+
+
+def _six_stats(stats) -> tuple:
+    """A Calibration or six numbers as six Python floats holding float32 values, msv_hmm_stats' order."""
+    six = np.asarray(stats.stats if isinstance(stats, Calibration) else stats, np.float32)
+    if six.shape != (6,):
+        raise ValueError("stats is a Calibration or six floats")
+    return tuple(float(x) for x in six)
+
+
+def _file_stats(profile: Profile_HMM) -> np.ndarray:
+    return np.array([profile.stats_local_msv_mu, profile.stats_local_msv_lambda, profile.stats_local_viterbi_mu,
+                     profile.stats_local_viterbi_lambda, profile.stats_local_forward_theta,
+                     profile.stats_local_forward_lambda], np.float32)
+
+
+_CAL_SETS = ("msv", "viterbi", "forward")
+
+
+def _cal_triple(value, what: str) -> tuple:
+    """n= / length=: None (the defaults), one number for every set, or one per set (MSV, Viterbi, Forward)."""
+    if value is None:
+        return (0, 0, 0)
+    if np.ndim(value) == 0:
+        return (int(value),) * 3
+    if len(value) != 3:
+        raise ValueError(f"{what} is one number or three")
+    return tuple(int(v) for v in value)
+
+
+def _calibrate(call, profile, engines, n, length, tail, seed, workspace_bytes, insert_mode, keep_scores):
+    opt = _native.CalOptions(_cal_triple(n, "n"), _cal_triple(length, "length"), tail, seed, insert_mode,
+                             workspace_bytes)
+    from_file = _file_stats(profile)
+    stats = from_file.copy()
+    rep = _native.CalReport()
+    scores = {}
+    if keep_scores:
+        for s, name in enumerate(_CAL_SETS):
+            if engines[s]:
+                scores[name] = np.zeros(opt.n[s] or (200, 200, 200)[s], np.float32)
+                opt.scores[s] = scores[name].ctypes.data
+    check(call(opt, stats, rep), "calibrate")
+    report = rep.as_dict()
+    report["lambda"] = report.pop("lambda_")
+    return Calibration(stats, rep.lambda_, report, from_file, scores)
+
+
+def calibrate(profile: Profile_HMM, msv_engine: "MSV_HMM | None" = None, vit_engine: "Viterbi_HMM | None" = None,
+              fwd_engine: "Forward_HMM | None" = None, *, n=None, length=None, tail: float = 0.04, seed: int = 42,
+              workspace_bytes: int = 0, keep_scores: bool = False) -> Calibration:
+    """HMMER3's p7_Calibrate for this library's engines, on the GPU (msv_cal_calibrate): per engine given, a null
+    sample of n iid background sequences of `length` residues (defaults 200 x 200, 200 x 200, 200 x 100; one number
+    for all three sets or one per set) is generated on the device, scored by the engine and fitted there: the MSV and
+    Viterbi mu at the profile's lambda, the Forward tau from a complete Gumbel fit and the tail mass.  An engine that
+    is None is skipped and its two slots keep the file's values.  The profile's own statistics are not modified."""
+    L = _native.lib()
+    engines = (msv_engine, vit_engine, fwd_engine)
+    ptrs = [e._p if e is not None else None for e in engines]
+    return _calibrate(lambda opt, stats, rep: L.msv_cal_calibrate(profile._h, *ptrs, C.byref(opt), stats.ctypes.data,
+                                                                  C.byref(rep)),
+                      profile, engines, n, length, tail, seed, workspace_bytes, 0, keep_scores)
+
+
+def cal_cpu_calibrate(profile: Profile_HMM, sets=_CAL_SETS, *, insert_mode: int = INSERTS_ZERO, n=None, length=None,
+                      tail: float = 0.04, seed: int = 42, keep_scores: bool = False) -> Calibration:
+    """The CPU twin of calibrate() (msv_cal_cpu_calibrate): the same sample, the CPU DPs, the host fits."""
+    L = _native.lib()
+    run = tuple(name in sets for name in _CAL_SETS)
+    mask = sum(1 << s for s in range(3) if run[s])
+    return _calibrate(lambda opt, stats, rep: L.msv_cal_cpu_calibrate(profile._h, mask, C.byref(opt),
+                                                                      stats.ctypes.data, C.byref(rep)),
+                      profile, run, n, length, tail, seed, 0, insert_mode, keep_scores)
+
+
+def cal_lambda(profile: Profile_HMM) -> float:
+    """The profile's lambda from its match emissions and the background (msv_cal_lambda, HMMER's p7_Lambda)."""
+    em = np.ascontiguousarray(profile.match_emissions, np.float32)
+    out = C.c_double()
+    check(_native.lib().msv_cal_lambda(em.ctypes.data, profile.model_length,
+                                       background_frequencies().ctypes.data, C.byref(out)), "msv_cal_lambda")
+    return out.value
+
+
+def cal_thresholds(background=None) -> np.ndarray:
+    """The 19 thresholds of the null sample's draw (msv_cal_thresholds) -> uint32[19]."""
+    bg = np.ascontiguousarray(background_frequencies() if background is None else background, np.float32)
+    out = np.zeros(19, np.uint32)
+    check(_native.lib().msv_cal_thresholds(bg.ctypes.data, out.ctypes.data), "msv_cal_thresholds")
+    return out
+
+
+def cal_codes_of_draws(draws, background=None) -> np.ndarray:
+    """The residue codes of 24-bit draws (msv_cal_codes_of_draws) -> uint8[n]."""
+    bg = np.ascontiguousarray(background_frequencies() if background is None else background, np.float32)
+    draws = np.ascontiguousarray(draws, np.uint32)
+    out = np.zeros(draws.size, np.uint8)
+    check(_native.lib().msv_cal_codes_of_draws(bg.ctypes.data, _ptr(draws), draws.size, _ptr(out)),
+          "msv_cal_codes_of_draws")
+    return out
+
+
+def cal_generate(seed: int, set: int, first: int, n: int, length: int, background=None):
+    """THE null sample (msv_cal_generate): sequences first .. first + n - 1 of a sample set -> (codes, offsets)."""
+    bg = np.ascontiguousarray(background_frequencies() if background is None else background, np.float32)
+    codes = np.zeros(n * length, np.uint8)
+    offsets = np.zeros(n + 1, np.uint64)
+    check(_native.lib().msv_cal_generate(bg.ctypes.data, seed & (2 ** 64 - 1), set, first, n, length, _ptr(codes),
+                                         offsets.ctypes.data), "msv_cal_generate")
+    return codes, offsets
+
+
+def cal_fit_location(scores, lam: float, length: int = 0) -> float:
+    """mu of a Gumbel of known lambda (msv_cal_fit_location); length = 0: the scores are bit scores already."""
+    scores = np.ascontiguousarray(scores, np.float32)
+    out = C.c_double()
+    check(_native.lib().msv_cal_fit_location(_ptr(scores), scores.size, length, lam, C.byref(out)),
+          "msv_cal_fit_location")
+    return out.value
+
+
+def cal_fit_gumbel(scores, length: int = 0):
+    """The complete Gumbel fit (msv_cal_fit_gumbel) -> (mu, lambda, Newton iterations)."""
+    scores = np.ascontiguousarray(scores, np.float32)
+    mu, lam, it = C.c_double(), C.c_double(), C.c_uint32()
+    check(_native.lib().msv_cal_fit_gumbel(_ptr(scores), scores.size, length, C.byref(mu), C.byref(lam),
+                                           C.byref(it)), "msv_cal_fit_gumbel")
+    return mu.value, lam.value, it.value
+
+
+def cal_tau(gmu: float, glam: float, lam: float, tail: float = 0.04) -> float:
+    """Forward's tau from the fitted Gumbel, the profile's lambda and the tail mass (msv_cal_tau, HMMER's p7_Tau)."""
+    out = C.c_double()
+    check(_native.lib().msv_cal_tau(gmu, glam, lam, tail, C.byref(out)), "msv_cal_tau")
+    return out.value
+
+
+def write_hmm_stats(src_path: str, dst_path: str, stats) -> None:
+    """Copies a profile's text with its three STATS LOCAL lines rewritten, in the file's own format, to the given six
+    (a Calibration or six floats): a calibrated profile saved for the unchanged parser.  Every other byte is kept."""
+    six = _six_stats(stats)
+    form = {"MSV": "STATS LOCAL MSV      %8.4f %8.5f", "VITERBI": "STATS LOCAL VITERBI  %8.4f %8.5f",
+            "FORWARD": "STATS LOCAL FORWARD  %8.4f %8.5f"}
+    slot = {"MSV": 0, "VITERBI": 2, "FORWARD": 4}
+    with open(src_path, "r", encoding="latin-1", newline="") as f:
+        lines = f.read().split("\n")
+    seen = set()
+    for i, line in enumerate(lines):
+        w = line.split()
+        if len(w) >= 3 and w[0] == "STATS" and w[1] == "LOCAL" and w[2] in form and w[2] not in seen:
+            seen.add(w[2])
+            lines[i] = form[w[2]] % (six[slot[w[2]]], six[slot[w[2]] + 1]) + ("\r" if line.endswith("\r") else "")
+        if line.startswith("HMM "):
+            break
+    if len(seen) != 3:
+        raise ValueError(f"{src_path} has no three STATS LOCAL lines")
+    with open(dst_path, "w", encoding="latin-1", newline="") as f:
+        f.write("\n".join(lines))
+
+
 def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Forward_HMM,
                     seqs: Sequence[str] | None = None, *, codes: np.ndarray | None = None,
                     offsets: np.ndarray | None = None, F1: float = 0.02, F2: float = 1e-3,
                     dom_engine: "Domain_HMM | None" = None, F3: float = 1e-5, align: bool = False,
-                    null2: bool = False, bias_engine: "Bias_filter | None" = None, split: bool = False) -> dict:
+                    null2: bool = False, bias_engine: "Bias_filter | None" = None, split: bool = False,
+                    stats=None) -> dict:
     """HMMER3's whole cascade on the GPU (msv_fwd_filter_batch): MSV over every sequence, P <= F1, Viterbi on the
     survivors, P <= F2, Forward on those, Forward P-values.  Returns the per-stage arrays: msv_scores, passed_msv,
     vit_scores (-inf where not run), passed_vit, fwd_scores (-inf where not run), fwd_pvalues (1 where not run).
@@ -1447,14 +1633,20 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
     With split=True (which needs align=True; msv.h "Split stage") the regions are first put through
     Domain_HMM.split_regions: a multi-domain region is sampled and clustered, "alignments" holds one item per cluster
     envelope in place of the region, and the dict gains "split" (split_regions' dict: which region each item came
-    from and its prob).  With split=False no launch or allocation is added and every returned byte is unchanged."""
+    from and its prob).  With split=False no launch or allocation is added and every returned byte is unchanged.
+    stats (a Calibration, e.g. calibrate()'s, or six floats in msv_hmm_stats' order) takes the place of the engines'
+    file values everywhere they go: the three tests, fwd_pvalues and null2's bias_scores.  With stats=None no byte of
+    any result changes and no launch is added."""
     if null2 and not align:
         raise ValueError("null2=True needs align=True")
     if split and not align:
         raise ValueError("split=True needs align=True")
     codes, offsets, n = _batch(seqs, codes, offsets)
-    stats = np.array([msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
-                      fwd_engine.forward_tau, fwd_engine.forward_lambda], np.float32)
+    if stats is None:
+        stats = np.array([msv_engine.msv_mu, msv_engine.msv_lambda, vit_engine.viterbi_mu, vit_engine.viterbi_lambda,
+                          fwd_engine.forward_tau, fwd_engine.forward_lambda], np.float32)
+    else:
+        stats = np.array(_six_stats(stats), np.float32)
     msc, vsc, fsc = (np.zeros(n, np.float32) for _ in range(3))
     p1, p2 = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
     fpv = np.zeros(n, np.float64)
@@ -1488,7 +1680,7 @@ def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Fo
                 out["alignments"] = dom_engine.align_batch(codes=codes, offsets=offsets,
                                                            envelopes=out["envelopes"], null2=null2)
             if null2:
-                b = out["alignments"].bias_scores(fwd_engine.forward_tau, fwd_engine.forward_lambda, fwd_scores=fsc)
+                b = out["alignments"].bias_scores(float(stats[4]), float(stats[5]), fwd_scores=fsc)
                 out["domain_bits"], out["domain_pvalues"] = b["domain_bits"], b["domain_pvalues"]
                 for k in ("seq_bias", "seq_bits", "seq_pvalues"):
                     out[k] = b[k][hits]

@@ -25,6 +25,7 @@ STATUS = {
     8: "MSV_ERR_HIP",
     9: "MSV_ERR_OUT_OF_MEMORY",
     10: "MSV_ERR_RCCL",
+    11: "MSV_ERR_NO_CONVERGENCE",
 }
 MSV_OK = 0
 MSV_ERR_BAD_RESIDUE = 4
@@ -83,7 +84,11 @@ EXPORTED = [
     "msv_dom_is_multidomain", "msv_spl_cpu_forward", "msv_spl_sample", "msv_spl_cluster", "msv_spl_item_bytes",
     "msv_spl_sample_batch", "msv_spl_result_count", "msv_spl_result_segments", "msv_spl_result_copy",
     "msv_spl_result_matrix", "msv_spl_result_stats", "msv_spl_result_free", "msv_spl_describe",
+    "msv_cal_lambda", "msv_cal_thresholds", "msv_cal_codes_of_draws", "msv_cal_generate", "msv_cal_fit_location",
+    "msv_cal_fit_gumbel", "msv_cal_tau", "msv_cal_cpu_calibrate", "msv_cal_workspace_bytes",
+    "msv_cal_generate_device", "msv_cal_fit_device", "msv_cal_calibrate",
 ]
+CAL_FIT_LOCATION, CAL_FIT_GUMBEL, CAL_FIT_TAU = 0, 1, 2  # msv.h msv_cal_fit_mode
 BF_GUMBEL, BF_EXPONENTIAL = 0, 1  # msv.h MSV_BF_*: the tail of a filtered P-value
 
 
@@ -313,6 +318,39 @@ class SplInfo(C.Structure):
         d["variant"] = self.variant.decode()
         return d
 
+
+class CalOptions(C.Structure):
+    """msv_cal_options: append-only, struct_size first (set on construction); index = sample set."""
+    _fields_ = [("struct_size", C.c_uint64), ("n", C.c_uint64 * 3), ("length", C.c_uint64 * 3), ("tail", C.c_double),
+                ("seed", C.c_uint64), ("seed_set", C.c_int32), ("insert_mode", C.c_int32),
+                ("workspace_bytes", C.c_uint64), ("scores", C.c_void_p * 3)]
+
+    def __init__(self, n=(0, 0, 0), length=(0, 0, 0), tail=0.0, seed=42, insert_mode=0, workspace_bytes=0):
+        super().__init__(C.sizeof(CalOptions), (C.c_uint64 * 3)(*n), (C.c_uint64 * 3)(*length), tail,
+                         seed & (2 ** 64 - 1), 1, insert_mode, workspace_bytes)
+
+
+class CalReport(C.Structure):
+    """msv_cal_report: append-only, struct_size first (set before the call)."""
+    _fields_ = [("struct_size", C.c_uint32), ("ran", C.c_uint32), ("lambda_", C.c_double),
+                ("location", C.c_double * 3), ("gmu", C.c_double), ("glam", C.c_double),
+                ("iterations", C.c_uint32), ("reserved", C.c_uint32), ("chunks", C.c_uint64 * 3),
+                ("n", C.c_uint64 * 3), ("length", C.c_uint64 * 3), ("seed", C.c_uint64), ("tail", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(CalReport)
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f not in ("struct_size", "reserved")}
+        for f in ("location", "chunks", "n", "length"):
+            d[f] = list(d[f])
+        return d
+
+
+# msv_cal_fit, the fit kernel's record, as a numpy structured dtype (40 bytes)
+CAL_FIT_DTYPE = [("mu", "<f8"), ("lambda_", "<f8"), ("gmu", "<f8"), ("glam", "<f8"), ("iterations", "<u4"),
+                 ("status", "<u4")]
 
 # msv_spl_segment and msv_spl_envelope as numpy structured dtypes
 SEGMENT_DTYPE = [("i_from", "<u4"), ("i_to", "<u4"), ("k_from", "<u4"), ("k_to", "<u4")]
@@ -616,6 +654,19 @@ def lib() -> C.CDLL:
         "msv_spl_result_stats": (C.c_int, [vp, C.POINTER(SplStats)]),
         "msv_spl_result_free": (None, [vp]),
         "msv_spl_describe": (C.c_int, [vp, C.POINTER(SplInfo)]),
+        "msv_cal_lambda": (C.c_int, [vp, u32, vp, C.POINTER(C.c_double)]),
+        "msv_cal_thresholds": (C.c_int, [vp, vp]),
+        "msv_cal_codes_of_draws": (C.c_int, [vp, vp, u64, vp]),
+        "msv_cal_generate": (C.c_int, [vp, u64, u32, u64, u64, u64, vp, vp]),
+        "msv_cal_fit_location": (C.c_int, [vp, u64, u64, C.c_double, C.POINTER(C.c_double)]),
+        "msv_cal_fit_gumbel": (C.c_int, [vp, u64, u64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.POINTER(u32)]),
+        "msv_cal_tau": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+        "msv_cal_cpu_calibrate": (C.c_int, [vp, u32, C.POINTER(CalOptions), vp, C.POINTER(CalReport)]),
+        "msv_cal_workspace_bytes": (u64, [u64, u64]),
+        "msv_cal_generate_device": (C.c_int, [C.c_int, vp, u64, u32, u64, u64, u64, vp, vp, vp]),
+        "msv_cal_fit_device": (C.c_int, [C.c_int, vp, u64, u64, C.c_int, C.c_double, C.c_double, vp, vp]),
+        "msv_cal_calibrate": (C.c_int, [vp, vp, vp, vp, C.POINTER(CalOptions), vp, C.POINTER(CalReport)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

@@ -40,7 +40,8 @@ typedef enum msv_status {
     MSV_ERR_NO_DEVICE = 7,        /* no HIP device / bad device ordinal                        */
     MSV_ERR_HIP = 8,              /* a HIP runtime call failed                                 */
     MSV_ERR_OUT_OF_MEMORY = 9,
-    MSV_ERR_RCCL = 10             /* an RCCL call failed (multi-GPU context)                   */
+    MSV_ERR_RCCL = 10,            /* an RCCL call failed (multi-GPU context)                   */
+    MSV_ERR_NO_CONVERGENCE = 11   /* an iterative fit did not converge (calibration, msv_cal_fit_gumbel) */
 } msv_status;
 
 typedef struct msv_hmm msv_hmm;         /* parsed HMMER3 profile (host)            */
@@ -1273,6 +1274,120 @@ typedef struct msv_spl_info {
     char variant[64];
 } msv_spl_info;
 msv_status msv_spl_describe(const msv_dom_profile* profile, msv_spl_info* out);
+
+/* ---- Calibration: the engines' own mu, tau and lambda ------------------------------------------
+ * Every P-value of this library goes through the three pairs STATS LOCAL MSV / VITERBI / FORWARD of the .hmm file,
+ * which hmmbuild fitted to HMMER3's own 8-bit and 16-bit filters, not to this library's float engines.  This block
+ * restates HMMER3's p7_Calibrate for the engines here: a null sample is generated, scored by the engines and
+ * fitted, all on the device.  As for every stage since Viterbi, parity with HMMER is unpinned.  The file's own
+ * statistics are never modified: the fitted six are returned, and the cascade takes them in place of the file's.
+ *
+ * Lambda (p7_Lambda), float64: H = (1 / LENG) sum_k sum_x p_k[x] log2(p_k[x] / f[x]) over the parsed match
+ * emissions of nodes 1..LENG (terms with p = 0 are 0) and the background f; lambda = ln 2 + 1.44 / (LENG H).
+ *
+ * The null sample.  Residue i (0-based) of sequence s of sample set `set` (0 MSV, 1 Viterbi, 2 Forward) under `seed`:
+ * with mix and g of the split stage's random numbers, h = seed, h = mix(h + g + set), h = mix(h + g + s);
+ * u = mix(h + g (i + 1)) >> 40 (24 bits); code = the number of j in 0..18 with u >= T[j], where
+ * T[j] = (uint32) floor(2^24 (f[0] + .. + f[j]) / (f[0] + .. + f[19])), the sums in float64 in index order.
+ * Integers only and no state: any slice of any chunk is reproducible.  msv_cal_generate is THE definition; the
+ * device kernel's bytes equal it.
+ *
+ * The fits, float64 over float32 bit scores x_i = bits_of(score_i - nullsc(L)) (the float expressions of
+ * msv_pvalues; L = 0 means the scores ARE bit scores and are taken as they are).  y_i = x_i - x_min.
+ *   location at fixed lambda (esl_gumbel_FitCompleteLoc; MSV, Viterbi):
+ *       mu = x_min - log((1 / n) sum_i exp(-lambda y_i)) / lambda
+ *   complete fit (esl_gumbel_FitComplete; Forward): lambda0 = pi / sqrt(6 var), var = sum (y_i - ybar)^2 / (n - 1);
+ *       Newton on f(l) = 1 / l - ybar + S1 / S0, f'(l) = (S1 / S0)^2 - S2 / S0 - 1 / l^2, S_p = sum y_i^p exp(-l y_i):
+ *       each iteration evaluates (f, f') at l, takes step = f / f', moves to l - step (or to l / 2 where that is
+ *       <= 0) and stops when |step| <= 1e-9 l; after 100 iterations without that, MSV_ERR_NO_CONVERGENCE (also for a
+ *       lambda that stops being finite).  There is no fallback.  mu is the location formula at the final lambda.
+ *   tau (p7_Tau): tau = gmu - log(-log(1 - t)) / glam + log(t) / lambda_profile, (gmu, glam) the complete fit,
+ *       t the tail mass (default 0.04).
+ * n < 2, all scores equal (zero variance), a bit score that is not finite, lambda <= 0 or a tail outside (0, 1):
+ * MSV_ERR_INVALID_ARGUMENT.  Order of summation, fixed: the host adds in index order; the device kernel (one
+ * workgroup of 256 threads) has thread t add elements t, t + 256, .. in index order and then halves an LDS tree
+ * (t += t + 128, 64, .., 1).  Neither depends on the run.  DESIGN 4.15 derives the bounds between the two. */
+enum { MSV_CAL_SET_MSV = 0, MSV_CAL_SET_VITERBI = 1, MSV_CAL_SET_FORWARD = 2 };
+typedef enum msv_cal_fit_mode {
+    MSV_CAL_FIT_LOCATION = 0, /* mu at the given lambda                                         */
+    MSV_CAL_FIT_GUMBEL = 1,   /* the complete fit: (mu, lambda)                                 */
+    MSV_CAL_FIT_TAU = 2       /* the complete fit, then tau at the given lambda and tail        */
+} msv_cal_fit_mode;
+/* The record the fit kernel writes (40 bytes).  LOCATION: mu, lambda as given (gmu, glam repeat them).  GUMBEL:
+ * mu = gmu, lambda = glam.  TAU: mu = tau, lambda as given, (gmu, glam) the fitted Gumbel.  status is a msv_status;
+ * where it is not MSV_OK the four doubles are NaN. */
+typedef struct msv_cal_fit {
+    double mu, lambda, gmu, glam;
+    uint32_t iterations;      /* Newton iterations (0 for LOCATION) */
+    uint32_t status;
+} msv_cal_fit;
+/* Append-only: struct_size is set by the caller; fields beyond it read as 0 and 0 means the default.  Index = set. */
+typedef struct msv_cal_options {
+    uint64_t struct_size;
+    uint64_t n[3];            /* sequences: HMMER's 200, 200, 200                                          */
+    uint64_t length[3];       /* their length: HMMER's 200, 200, 100                                       */
+    double tail;              /* tail mass of tau: 0.04                                                    */
+    uint64_t seed;            /* used as given when seed_set, else 42                                      */
+    int32_t seed_set;
+    int32_t insert_mode;      /* msv_cal_cpu_calibrate only: the engines' (the device call's engines hold theirs) */
+    uint64_t workspace_bytes; /* device bytes of a chunk's residues and offsets (0 = 256 MiB)              */
+    float* scores[3];         /* optional host arrays of n[set] floats: the set's raw scores (nats), copied out
+                                 after the fit for tests and tools                                         */
+} msv_cal_options;
+/* Append-only, struct_size set by the caller. */
+typedef struct msv_cal_report {
+    uint32_t struct_size;
+    uint32_t ran;             /* bit s: set s was run                                                      */
+    double lambda;            /* the profile's (msv_cal_lambda)                                            */
+    double location[3];       /* MSV mu, Viterbi mu, Forward tau (NaN where not run)                       */
+    double gmu, glam;         /* the Gumbel fitted to the Forward sample                                   */
+    uint32_t iterations;      /* of that fit's Newton loop                                                 */
+    uint32_t reserved;
+    uint64_t chunks[3];       /* generate + score launches per set                                         */
+    uint64_t n[3], length[3]; /* as run                                                                    */
+    uint64_t seed;
+    double tail;
+} msv_cal_report;
+
+/* Host-only.  match_emissions: [model_length][20] as msv_hmm_match_emissions (row 0 is the dummy node). */
+msv_status msv_cal_lambda(const float* match_emissions, uint32_t model_length, const float* background,
+                          double* lambda);
+/* The 19 thresholds T of the null sample, and the codes of n given 24-bit draws (the count rule above). */
+msv_status msv_cal_thresholds(const float* background, uint32_t* thresholds);
+msv_status msv_cal_codes_of_draws(const float* background, const uint32_t* draws, uint64_t n, uint8_t* codes);
+/* THE definition of the null sample: sequences first .. first + n - 1 of `set`, each of L residues, as a CSR batch:
+ * codes[n L], offsets[n + 1] = 0, L, 2 L, ..  L must be below 2^32 - 1. */
+msv_status msv_cal_generate(const float* background, uint64_t seed, uint32_t set, uint64_t first, uint64_t n,
+                            uint64_t L, uint8_t* codes, uint64_t* offsets);
+msv_status msv_cal_fit_location(const float* scores, uint64_t n, uint64_t L, double lambda, double* mu);
+msv_status msv_cal_fit_gumbel(const float* scores, uint64_t n, uint64_t L, double* mu, double* lambda,
+                              uint32_t* iterations);
+msv_status msv_cal_tau(double gmu, double glam, double lambda, double tail, double* tau);
+/* The CPU twin of msv_cal_calibrate: the same sample from msv_cal_generate, scored by the CPU paths (the MSV DP
+ * of MSV_HMM::run_on_sequence, msv_vit_cpu_score's, msv_fwd_cpu_score_batch rounded to float) and fitted on the
+ * host.  sets: bit s runs set s; the others' slots of stats stay as the caller filled them. */
+msv_status msv_cal_cpu_calibrate(const msv_hmm* hmm, uint32_t sets, const msv_cal_options* options, float* stats,
+                                 msv_cal_report* report);
+
+/* Device bytes of a chunk of n sequences of length L: the codes rounded up to 16 bytes, then n + 1 offsets. */
+uint64_t msv_cal_workspace_bytes(uint64_t n, uint64_t L);
+/* msv_cal_generate on the device, enqueued on `stream` (a hipStream_t; not NULL): one thread writes 16
+ * consecutive code bytes with one vector store (the ragged end in byte stores), the same launch the offsets.
+ * d_codes must be 16-byte aligned with room for n L bytes, n L < 2^32 - 2^20. */
+msv_status msv_cal_generate_device(int device, const float* background, uint64_t seed, uint32_t set, uint64_t first,
+                                   uint64_t n, uint64_t L, uint8_t* d_codes, uint64_t* d_offsets, void* stream);
+/* One fit launch (a single workgroup) over n device scores; writes *d_record.  Nothing is read back: the record's
+ * status word carries the fit's errors. */
+msv_status msv_cal_fit_device(int device, const float* d_scores, uint64_t n, uint64_t L, int mode, double lambda,
+                              double tail, msv_cal_fit* d_record, void* stream);
+/* The stage.  Per engine that is not NULL: the set's N sequences are generated in chunks that fit the workspace
+ * (and the engines' limit of 2^32 - 2^20 residue bytes per call), each chunk scored by the engine's device call
+ * into the set's N-float array, then one fit launch; nothing crosses PCIe between the seed and the result record.
+ * On its own stream; the engines' length tables are reserved for L and their latched errors returned through
+ * their check calls.  stats: msv_hmm_stats' six; a NULL engine leaves its two slots as the caller filled them;
+ * each lambda slot written is the profile's lambda.  report may be NULL.  The engines must live on one device. */
+msv_status msv_cal_calibrate(const msv_hmm* hmm, msv_profile* msv, msv_vit_profile* vit, msv_fwd_profile* fwd,
+                             const msv_cal_options* options, float* stats, msv_cal_report* report);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -385,3 +385,27 @@ class Bias_filter {
     Probabilities_array<NUM_OF_AMINO_ACIDS> compo_{};
     msv_bf_profile* profile_ = nullptr;
 };
+
+// Calibration (msv.h "Calibration"): HMMER3's p7_Calibrate for this library's engines, on the GPU.
+// stats is msv_hmm_stats' six with the slots of every engine given replaced by the fitted values (a null engine keeps
+// the file's); from_file the file's own six; report the float64 values.  Header-only: one C-ABI call.
+struct Calibration {
+    std::array<float, 6> stats{};
+    std::array<float, 6> from_file{};
+    msv_cal_report report{};
+};
+inline Calibration calibrate(const std::string& file_path, MSV_HMM* msv_engine, Viterbi_HMM* vit_engine,
+                             Forward_HMM* fwd_engine, const msv_cal_options* options = nullptr) {
+    msv_hmm* h = nullptr;
+    msv_status s = msv_hmm_read(file_path.c_str(), &h);
+    if (s != MSV_OK) throw msv_error(s, std::string(msv_status_string(s)) + ": " + file_path);
+    Calibration c;
+    msv_hmm_stats(h, c.from_file.data());
+    c.stats = c.from_file;
+    c.report.struct_size = sizeof(c.report);
+    s = msv_cal_calibrate(h, msv_engine ? msv_engine->handle() : nullptr, vit_engine ? vit_engine->handle() : nullptr,
+                          fwd_engine ? fwd_engine->handle() : nullptr, options, c.stats.data(), &c.report);
+    msv_hmm_destroy(h);
+    if (s != MSV_OK) throw msv_error(s, std::string("msv_cal_calibrate: ") + msv_status_string(s));
+    return c;
+}
