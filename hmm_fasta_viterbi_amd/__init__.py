@@ -17,6 +17,8 @@ Python mirror of the reference's C++ class surface, bound to libmsv_hip.so (incl
                                              alignment of each envelope)
     calibrate(profile, msv, vit, fwd)       (new, DESIGN 4.15: the engines' own mu, tau and lambda, fitted on the GPU;
                                              search_pipeline(..., stats=) takes them in place of the file's)
+    Emitter(profile).emit(n)                (new, DESIGN 4.16: sequences drawn from the profile on the GPU, with the
+                                             true domains and ops of each as a Traces)
 
 Sequences use the reference's form ('#' sentinel + one-letter residues) or packed codes
 0..19 (alphabetical A C D E F G H I K L M N P Q R S T V W Y) with CSR offsets.
@@ -40,6 +42,7 @@ __all__ = [
     "Alignments", "aln_oa", "Bias_filter", "background_frequencies", "Ensembles", "dom_is_multidomain", "spl_cluster",
     "spl_sample", "Calibration", "calibrate", "cal_cpu_calibrate", "cal_lambda", "cal_thresholds",
     "cal_codes_of_draws", "cal_generate", "cal_fit_location", "cal_fit_gumbel", "cal_tau", "write_hmm_stats",
+    "Emitter", "Emitted", "emit_generate", "emit_path_score", "emit_tables",
 ]
 
 INSERTS_ZERO = 0      # HMMER3's insert scores (background emissions: 0)
@@ -1607,6 +1610,241 @@ def write_hmm_stats(src_path: str, dst_path: str, stats) -> None:
         raise ValueError(f"{src_path} has no three STATS LOCAL lines")
     with open(dst_path, "w", encoding="latin-1", newline="") as f:
         f.write("\n".join(lines))
+
+
+class Emitted:
+    """What Emitter.emit / cpu_emit return (msv.h "Emit stage"): the CSR batch `codes` uint8 and `offsets`
+    uint64 [n + 1], `truncated` bool [n], `traces` -- the true paths as a Traces (domains, ops; scores =
+    msv_emit_path_score under the engines' tables), None where truth was not asked for -- and `chunks`, the device
+    chunks the call ran (0 for the host definition)."""
+
+    def __init__(self, codes, offsets, truncated, traces, chunks=0):
+        self.codes, self.offsets, self.truncated, self.traces, self.chunks = codes, offsets, truncated, traces, chunks
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def sequences(self) -> list[str]:
+        """The batch in the reference's form: '#' + one-letter residues."""
+        letters = np.frombuffer(AMINO_ACIDS.encode(), np.uint8)[self.codes].tobytes().decode()
+        return ["#" + letters[int(self.offsets[i]):int(self.offsets[i + 1])] for i in range(len(self))]
+
+
+def _emit_take(handle, with_truth: bool):
+    """An msv_emit_result as numpy arrays (and frees it) -> (codes, offsets, domain_offsets, domains, ops, truncated,
+    chunks)."""
+    L = _native.lib()
+    try:
+        n = int(L.msv_emit_result_count(handle))
+        codes = np.zeros(int(L.msv_emit_result_residues(handle)), np.uint8)
+        offsets = np.zeros(n + 1, np.uint64)
+        dom_off = np.zeros(n + 1, np.uint64)
+        doms = np.zeros(int(L.msv_emit_result_domains(handle)) if with_truth else 0, _native.DOMAIN_DTYPE)
+        ops = np.zeros(int(L.msv_emit_result_ops(handle)) if with_truth else 0, np.uint8)
+        trunc = np.zeros(n, np.uint8)
+        check(L.msv_emit_result_copy(handle, _ptr(codes), offsets.ctypes.data, dom_off.ctypes.data, _ptr(doms),
+                                     _ptr(ops), _ptr(trunc)), "msv_emit_result_copy")
+        return codes, offsets, dom_off, doms, ops, trunc.astype(bool), int(L.msv_emit_result_chunks(handle))
+    finally:
+        L.msv_emit_result_free(handle)
+
+
+def emit_tables(profile: Profile_HMM, length: int = 400, multihit: bool = True, insert_mode: int = INSERTS_ZERO,
+                max_length: int | None = None) -> dict:
+    """The emit stage's integer thresholds (msv_emit_tables): background uint32[19], match and insert [M, 19],
+    transitions [M, 4] = (T_MM, T_MM+MI, T_IM, T_DM), specials (T_loop, T_J)."""
+    M = profile.model_length
+    out = {"background": np.zeros(19, np.uint32), "match": np.zeros((M, 19), np.uint32),
+           "insert": np.zeros((M, 19), np.uint32), "transitions": np.zeros((M, 4), np.uint32),
+           "specials": np.zeros(2, np.uint32)}
+    opt = _native.EmitOptions(length, multihit, insert_mode, max_length)
+    check(_native.lib().msv_emit_tables(profile._h, C.byref(opt), *[a.ctypes.data for a in out.values()]),
+          "msv_emit_tables")
+    return out
+
+
+def emit_generate(profile: Profile_HMM, n: int, seed: int = 42, first: int = 0, *, length: int = 400,
+                  multihit: bool = True, insert_mode: int = INSERTS_ZERO, max_length: int | None = None):
+    """THE definition of the emit stage (msv_emit_generate): sequences first .. first + n - 1 drawn from the profile
+    -> (codes, offsets, domain_offsets, domains, ops, truncated)."""
+    opt = _native.EmitOptions(length, multihit, insert_mode, max_length)
+    h = C.c_void_p()
+    check(_native.lib().msv_emit_generate(profile._h, C.byref(opt), seed & (2 ** 64 - 1), first, n, C.byref(h)),
+          "msv_emit_generate")
+    return _emit_take(h, True)[:6]
+
+
+def emit_path_score(match_scores, insert_scores, transition_scores, consts, codes, domains, ops) -> float:
+    """The nats score of a given true path of one sequence (msv_emit_path_score): tables as msv_hmm_viterbi_scores
+    gives them (insert_scores None = zeros), consts = (tr_B_Mk, tr_E_C, tr_E_J), `domains` with ops_begin into `ops`."""
+    msc = np.ascontiguousarray(match_scores, np.float32)
+    isc = None if insert_scores is None else np.ascontiguousarray(insert_scores, np.float32)
+    tsc = np.ascontiguousarray(transition_scores, np.float32)
+    codes = np.ascontiguousarray(codes, np.uint8)
+    domains = np.ascontiguousarray(domains, _native.DOMAIN_DTYPE)
+    ops = np.ascontiguousarray(ops, np.uint8)
+    out = C.c_double()
+    _check_residues(_native.lib().msv_emit_path_score(
+        msc.ctypes.data, None if isc is None else isc.ctypes.data, tsc.ctypes.data, msc.shape[1],
+        *[float(x) for x in consts], _ptr(codes), codes.size, _ptr(domains), len(domains), _ptr(ops), C.byref(out)),
+        "msv_emit_path_score")
+    return out.value
+
+
+class Emitter:
+    """Sequences drawn from a profile on the GPU, with the paths that drew them (msv.h "Emit stage"): the
+    positive sample, the sibling of calibration's null sample.  It samples THIS library's scoring model run forwards
+    -- a fragment uniform over the LENG (LENG + 1) / 2 (k_start, k_end) pairs, not HMMER's occupancy-weighted entry --
+    so parity with hmmemit is unpinned.  `length` is the configured length Lc of the flanks (0: none), `multihit`
+    E -> J with 1/2, `insert_mode` where insert residues come from (INSERTS_ZERO: the background), `max_length` the
+    cut (None: 2^20).  A sequence depends on (seed, index, this configuration) only.  The device handle is made on
+    first use; cpu_emit, the definition, needs no GPU."""
+
+    def __init__(self, profile: Profile_HMM, length: int = 400, multihit: bool = True,
+                 insert_mode: int = INSERTS_ZERO, max_length: int | None = None, device: int = 0):
+        self._profile = profile
+        self.length, self.multihit, self.insert_mode, self.max_length = length, multihit, insert_mode, max_length
+        self.device = device
+        self._opt = _native.EmitOptions(length, multihit, insert_mode, max_length)
+        check(_native.lib().msv_emit_tables(profile._h, C.byref(self._opt), None, None, None, None, None),
+              "msv_emit_tables")
+        self._p = None
+        self._score_tables = None
+
+    def _handle(self):
+        if self._p is None:
+            p = C.c_void_p()
+            check(_native.lib().msv_emit_profile_create(self.device, self._profile._h, C.byref(self._opt),
+                                                        C.byref(p)), "msv_emit_profile_create")
+            self._p = p
+        return self._p
+
+    def _tables(self):
+        """The engines' tables the true paths are scored under (msv_hmm_viterbi_scores, this emitter's insert mode)."""
+        if self._score_tables is None:
+            M = self._profile.model_length
+            msc, isc, tsc = np.zeros((20, M), np.float32), np.zeros((20, M), np.float32), np.zeros((M, 7), np.float32)
+            b, c, j = C.c_float(), C.c_float(), C.c_float()
+            check(_native.lib().msv_hmm_viterbi_scores(self._profile._h, self.insert_mode, msc.ctypes.data,
+                                                       isc.ctypes.data, tsc.ctypes.data, C.byref(b), C.byref(c),
+                                                       C.byref(j)), "msv_hmm_viterbi_scores")
+            self._score_tables = (msc, isc if self.insert_mode else None, tsc, (b.value, c.value, j.value))
+        return self._score_tables
+
+    def path_scores(self, codes, offsets, domain_offsets, domains, ops) -> np.ndarray:
+        """msv_emit_path_score of every sequence of a batch with its truth -> float64 [n] (-inf: no domain)."""
+        msc, isc, tsc, consts = self._tables()
+        n = len(offsets) - 1
+        out = np.zeros(n, np.float64)
+        for q in range(n):
+            d = domains[int(domain_offsets[q]):int(domain_offsets[q + 1])]
+            out[q] = emit_path_score(msc, isc, tsc, consts, codes[int(offsets[q]):int(offsets[q + 1])], d, ops)
+        return out
+
+    def _emitted(self, taken, truth: bool, scores: bool) -> Emitted:
+        codes, offsets, dom_off, doms, ops, trunc, chunks = taken
+        traces = None
+        if truth:
+            sc = (self.path_scores(codes, offsets, dom_off, doms, ops) if scores
+                  else np.full(len(offsets) - 1, np.nan))
+            traces = Traces(sc, dom_off, doms, ops, stats={"chunks": chunks}, codes=codes, offsets=offsets)
+        return Emitted(codes, offsets, trunc, traces, chunks)
+
+    def cpu_emit(self, n: int, seed: int = 42, first: int = 0, scores: bool = True) -> Emitted:
+        """The definition (msv_emit_generate) on the host."""
+        h = C.c_void_p()
+        check(_native.lib().msv_emit_generate(self._profile._h, C.byref(self._opt), seed & (2 ** 64 - 1), first, n,
+                                              C.byref(h)), "msv_emit_generate")
+        return self._emitted(_emit_take(h, True), True, scores)
+
+    def emit(self, n: int, seed: int = 42, first: int = 0, truth: bool = True, workspace_bytes: int = 0,
+             stream: int | None = None, scores: bool = True) -> Emitted:
+        """Sequences first .. first + n - 1 on the GPU, downloaded (msv_emit_batch): in chunks that fit
+        workspace_bytes (0: 256 MiB); the bytes do not depend on the chunking and equal cpu_emit's.  scores=False
+        leaves the traces' scores NaN (msv_emit_path_score runs on the host, once per sequence)."""
+        h = C.c_void_p()
+        check(_native.lib().msv_emit_batch(self._handle(), seed & (2 ** 64 - 1), first, n, 1 if truth else 0,
+                                           workspace_bytes, stream, C.byref(h)), "msv_emit_batch")
+        return self._emitted(_emit_take(h, truth), truth, scores)
+
+    @staticmethod
+    def workspace_bytes(n: int, residues: int, domains: int, ops: int, truth: bool = True) -> int:
+        """Device bytes of one chunk holding these totals (msv_emit_workspace_bytes)."""
+        return int(_native.lib().msv_emit_workspace_bytes(n, residues, domains, ops, 1 if truth else 0))
+
+    def emit_into(self, n: int, codes_ptr: int, capacity: int, offsets_ptr: int, *, seed: int = 42, first: int = 0,
+                  truth: "_native.EmitTruth | None" = None, stream: int) -> dict:
+        """msv_emit_batch_device into the caller's device buffers (raw pointers), on `stream`; returns the totals
+        record.  MSVError MSV_ERR_OUT_OF_MEMORY (its .totals set) where a total exceeds its capacity: nothing was
+        written."""
+        tot = _native.EmitTotals()
+        st = _native.lib().msv_emit_batch_device(self._handle(), seed & (2 ** 64 - 1), first, n, codes_ptr, capacity,
+                                                 offsets_ptr, C.byref(truth) if truth is not None else None,
+                                                 C.byref(tot), stream)
+        if st != _native.MSV_OK:
+            err = MSVError(st, "msv_emit_batch_device")
+            err.totals = tot.as_dict()
+            raise err
+        return tot.as_dict()
+
+    def emit_device(self, n: int, seed: int = 42, first: int = 0, truth: bool = True,
+                    stream: int | None = None) -> dict:
+        """The batch left on the device for chaining into the engines' *_device calls: torch tensors sized by a first
+        call that only counts (capacity 0), then the call itself.  Returns the tensors (codes, offsets and, with truth,
+        domain_offsets, domains as raw bytes, ops, truncated), their pointers (codes_ptr, residues_len, offsets_ptr)
+        and the totals.  Needs torch."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_doff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_trunc = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        t = _native.EmitTruth(d_doff.data_ptr(), None, 0, None, 0, d_trunc.data_ptr()) if truth else None
+        torch.cuda.synchronize(dev)
+        try:
+            tot = self.emit_into(n, None, 0, d_off.data_ptr(), seed=seed, first=first, truth=t, stream=st)
+        except MSVError as e:
+            if e.name != "MSV_ERR_OUT_OF_MEMORY" or e.totals["residues"] >= (1 << 32) - (1 << 20):
+                raise
+            tot = e.totals
+        d_codes = torch.zeros(max(tot["residues"], 1), dtype=torch.uint8, device=dev)
+        out = {"codes": d_codes, "offsets": d_off}
+        if truth:
+            d_doms = torch.zeros(max(tot["domains"], 1) * 32, dtype=torch.uint8, device=dev)
+            d_ops = torch.zeros(max(tot["ops"], 1), dtype=torch.uint8, device=dev)
+            t = _native.EmitTruth(d_doff.data_ptr(), d_doms.data_ptr(), tot["domains"], d_ops.data_ptr(), tot["ops"],
+                                  d_trunc.data_ptr())
+            out.update(domain_offsets=d_doff, domains=d_doms, ops=d_ops, truncated=d_trunc[:n])
+        torch.cuda.synchronize(dev)
+        out["totals"] = self.emit_into(n, d_codes.data_ptr(), tot["residues"], d_off.data_ptr(), seed=seed,
+                                       first=first, truth=t, stream=st)
+        out.update(n=n, codes_ptr=d_codes.data_ptr(), residues_len=tot["residues"], offsets_ptr=d_off.data_ptr())
+        return out
+
+    def last_times(self) -> dict:
+        """Device times in ms of the last emit / emit_into call's count, scan and place launches (HIP events)."""
+        c, s, p = C.c_float(), C.c_float(), C.c_float()
+        check(_native.lib().msv_emit_profile_times(self._handle(), C.byref(c), C.byref(s), C.byref(p)),
+              "msv_emit_profile_times")
+        return {"count_ms": c.value, "scan_ms": s.value, "place_ms": p.value}
+
+    def bind_stream(self, stream: int | None) -> None:
+        """msv_emit_profile_bind_stream: emit()'s working stream where none is given (None: the handle's own)."""
+        check(_native.lib().msv_emit_profile_bind_stream(self._handle(), stream), "msv_emit_profile_bind_stream")
+
+    def describe(self) -> dict:
+        info = _native.EmitInfo()
+        check(_native.lib().msv_emit_describe(self._handle(), C.byref(info)), "msv_emit_describe")
+        return info.as_dict()
+
+    def close(self):
+        lib = _loaded_lib()
+        if getattr(self, "_p", None) and lib is not None:
+            lib.msv_emit_profile_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
 
 
 def search_pipeline(msv_engine: MSV_HMM, vit_engine: Viterbi_HMM, fwd_engine: Forward_HMM,

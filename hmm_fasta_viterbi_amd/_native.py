@@ -87,6 +87,11 @@ EXPORTED = [
     "msv_cal_lambda", "msv_cal_thresholds", "msv_cal_codes_of_draws", "msv_cal_generate", "msv_cal_fit_location",
     "msv_cal_fit_gumbel", "msv_cal_tau", "msv_cal_cpu_calibrate", "msv_cal_workspace_bytes",
     "msv_cal_generate_device", "msv_cal_fit_device", "msv_cal_calibrate",
+    "msv_emit_tables", "msv_emit_generate", "msv_emit_result_count", "msv_emit_result_residues",
+    "msv_emit_result_domains", "msv_emit_result_ops", "msv_emit_result_chunks", "msv_emit_result_copy",
+    "msv_emit_result_free", "msv_emit_path_score", "msv_emit_workspace_bytes", "msv_emit_profile_create",
+    "msv_emit_profile_destroy", "msv_emit_profile_bind_stream", "msv_emit_batch_device", "msv_emit_batch",
+    "msv_emit_describe", "msv_emit_profile_times",
 ]
 CAL_FIT_LOCATION, CAL_FIT_GUMBEL, CAL_FIT_TAU = 0, 1, 2  # msv.h msv_cal_fit_mode
 BF_GUMBEL, BF_EXPONENTIAL = 0, 1  # msv.h MSV_BF_*: the tail of a filtered P-value
@@ -346,6 +351,49 @@ class CalReport(C.Structure):
         for f in ("location", "chunks", "n", "length"):
             d[f] = list(d[f])
         return d
+
+
+class EmitOptions(C.Structure):
+    """msv_emit_options: append-only, struct_size first (set on construction)."""
+    _fields_ = [("struct_size", C.c_uint64), ("length", C.c_uint64), ("max_length", C.c_uint64),
+                ("length_set", C.c_int32), ("unihit", C.c_int32), ("insert_mode", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, length=400, multihit=True, insert_mode=0, max_length=None):
+        super().__init__(C.sizeof(EmitOptions), int(length), int(max_length or 0), 1, 0 if multihit else 1,
+                         insert_mode, 0)
+
+
+class EmitTotals(C.Structure):
+    """msv_emit_totals: the record the scan launch writes."""
+    _fields_ = [("residues", C.c_uint64), ("domains", C.c_uint64), ("ops", C.c_uint64), ("truncated", C.c_uint64),
+                ("overflow", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+class EmitTruth(C.Structure):
+    """msv_emit_truth: the truth buffers of a device call (device pointers, capacities in elements)."""
+    _fields_ = [("d_domain_offsets", C.c_void_p), ("d_domains", C.c_void_p), ("domains_capacity", C.c_uint64),
+                ("d_ops", C.c_void_p), ("ops_capacity", C.c_uint64), ("d_truncated", C.c_void_p)]
+
+
+class EmitInfo(C.Structure):
+    """msv_emit_info: append-only, struct_size first (set before the call)."""
+    _fields_ = [("struct_size", C.c_uint32), ("model_length", C.c_uint32), ("block", C.c_uint32),
+                ("scan_block", C.c_uint32), ("count_vgprs", C.c_uint32), ("place_vgprs", C.c_uint32),
+                ("scan_vgprs", C.c_uint32), ("count_scratch_bytes", C.c_uint32), ("place_scratch_bytes", C.c_uint32),
+                ("scan_scratch_bytes", C.c_uint32), ("count_lds_bytes", C.c_uint32), ("place_lds_bytes", C.c_uint32),
+                ("scan_lds_bytes", C.c_uint32), ("device", C.c_int), ("table_bytes", C.c_uint64),
+                ("length", C.c_uint64), ("max_length", C.c_uint64), ("unihit", C.c_int32), ("insert_mode", C.c_int32),
+                ("default_workspace_bytes", C.c_uint64)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(EmitInfo)
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "struct_size"}
 
 
 # msv_cal_fit, the fit kernel's record, as a numpy structured dtype (40 bytes)
@@ -667,6 +715,26 @@ def lib() -> C.CDLL:
         "msv_cal_generate_device": (C.c_int, [C.c_int, vp, u64, u32, u64, u64, u64, vp, vp, vp]),
         "msv_cal_fit_device": (C.c_int, [C.c_int, vp, u64, u64, C.c_int, C.c_double, C.c_double, vp, vp]),
         "msv_cal_calibrate": (C.c_int, [vp, vp, vp, vp, C.POINTER(CalOptions), vp, C.POINTER(CalReport)]),
+        "msv_emit_tables": (C.c_int, [vp, C.POINTER(EmitOptions), vp, vp, vp, vp, vp]),
+        "msv_emit_generate": (C.c_int, [vp, C.POINTER(EmitOptions), u64, u64, u64, C.POINTER(vp)]),
+        "msv_emit_result_count": (u64, [vp]),
+        "msv_emit_result_residues": (u64, [vp]),
+        "msv_emit_result_domains": (u64, [vp]),
+        "msv_emit_result_ops": (u64, [vp]),
+        "msv_emit_result_chunks": (u64, [vp]),
+        "msv_emit_result_copy": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "msv_emit_result_free": (None, [vp]),
+        "msv_emit_path_score": (C.c_int, [vp, vp, vp, u32, f32, f32, f32, vp, u64, vp, u32, vp,
+                                          C.POINTER(C.c_double)]),
+        "msv_emit_workspace_bytes": (u64, [u64, u64, u64, u64, C.c_int]),
+        "msv_emit_profile_create": (C.c_int, [C.c_int, vp, C.POINTER(EmitOptions), C.POINTER(vp)]),
+        "msv_emit_profile_destroy": (None, [vp]),
+        "msv_emit_profile_bind_stream": (C.c_int, [vp, vp]),
+        "msv_emit_batch_device": (C.c_int, [vp, u64, u64, u64, vp, u64, vp, C.POINTER(EmitTruth),
+                                            C.POINTER(EmitTotals), vp]),
+        "msv_emit_batch": (C.c_int, [vp, u64, u64, u64, C.c_int, u64, vp, C.POINTER(vp)]),
+        "msv_emit_describe": (C.c_int, [vp, C.POINTER(EmitInfo)]),
+        "msv_emit_profile_times": (C.c_int, [vp, fp, fp, fp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MSV_LIB_PATH") and not hasattr(L, name):

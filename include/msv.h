@@ -1389,6 +1389,152 @@ msv_status msv_cal_fit_device(int device, const float* d_scores, uint64_t n, uin
 msv_status msv_cal_calibrate(const msv_hmm* hmm, msv_profile* msv, msv_vit_profile* vit, msv_fwd_profile* fwd,
                              const msv_cal_options* options, float* stats, msv_cal_report* report);
 
+/* ---- Emit stage: sequences drawn from the profile, with their true paths ------------------------
+ * The positive sample, the sibling of calibration's null sample: the scoring model of the stages above run FORWARDS
+ * over the parsed probabilities (msv_hmm_match_emissions, msv_hmm_insert_emissions, msv_hmm_transitions, the
+ * background), on the device, into a CSR batch the engines' *_device calls take as it is, with each sequence's true
+ * domains and 'M' / 'I' / 'D' ops in the layout of the Viterbi traces (domain_offsets, msv_vit_domain, ops).
+ * This samples THIS LIBRARY's model: a fragment (k_start, k_end) is uniform over the LENG (LENG + 1) / 2 pairs -- the
+ * implicit local model a constant tr_B_Mk with free exits stands for -- not HMMER's occupancy-weighted entry, so
+ * parity with hmmemit / p7_ProfileEmit is unpinned, like every stage since Viterbi.
+ *
+ * Configuration: a configured length Lc (loop = Lc / (Lc + 3), move = 3 / (Lc + 3): the probabilities behind
+ * msv_sequence_transitions(Lc); Lc = 0 is legal and gives no flanks); multihit (E -> J with 1/2, E -> C with 1/2, the
+ * engines' nu = 2) or unihit (E -> C always, no draw); the insert mode (MSV_INSERTS_ZERO: insert residues from the
+ * background, as the engines score them; MSV_INSERTS_LOG_ODDS: from the file's insert emissions); max_length.
+ *
+ * The walk.  N: while a draw says loop, emit a residue from the background; then B.  B draws a fragment, 1 <= k_start
+ * <= k_end <= LENG; the core starts in M(k_start).  M(k) emits from match row k and, at k < k_end, draws among
+ * tMM / tMI / tMD of node k (to M(k+1), I(k), D(k+1)); I(k) emits, then draws tIM / tII (to M(k+1), I(k)); D(k) at
+ * k < k_end draws tDM / tDD (to M(k+1), D(k+1)); M(k_end) or D(k_end) goes to E (D -> E exits are the Forward
+ * model's).  Only transitions of nodes 1 .. LENG-1 are read, the Viterbi stage's rule, so no '*' entry is touched.
+ * E draws J or C (multihit).  J behaves as N, then B again; C behaves as N, then the walk ends.
+ *
+ * Integers only.  A categorical draw over weights w[0..c) compares a 24-bit draw u with the c - 1 thresholds
+ * T[j] = (uint32) floor(2^24 (w[0] + .. + w[j]) / (w[0] + .. + w[c-1])), float64 sums in index order (the count rule
+ * of msv_cal_thresholds): the category is the number of j with u >= T[j].  Groups, in this category order: loop /
+ * move; J / C; the 20 residues of the background, of a match row, of an insert row; MM / MI / MD, IM / II, DM / DD of
+ * a node.  A group whose total is not positive and finite gives MSV_ERR_INVALID_ARGUMENT when the tables are built.
+ * The fragment is a 32-bit draw r: index (r npairs) >> 32 into the pairs ordered by k_start, then k_end, decoded by
+ * an integer binary search over the cumulative counts C(s) = (s - 1) LENG - (s - 1)(s - 2) / 2 of the pairs before
+ * k_start = s.  Keys, with mix and g of the split stage's random numbers: h = seed, h = mix(h + g + MSV_EMIT_STREAM),
+ * h = mix(h + g + s) for sequence index s; draw d = 0, 1, .. of the walk, in the order the walk makes them, is
+ * mix(h + g (d + 1)) >> 40 (24 bits) or >> 32 (32 bits).  MSV_EMIT_STREAM is no sample set of calibration, so no
+ * key is shared with it.  A sequence depends on (seed, s, the configuration) and on nothing else.
+ *
+ * max_length: when the walk has emitted max_length residues it stops where it stands; an open domain is closed at
+ * the current node (so a truncated domain's last op may be 'I') and the sequence is flagged truncated.
+ *
+ * Truth.  Per sequence its domains (i_from, i_to: the first and last residue the domain emitted; k_from = k_start,
+ * k_to the exit node), one op byte per core state in path order; residues outside domains come from N, J, C.
+ * msv_emit_generate is THE definition; the device bytes equal it. */
+#define MSV_EMIT_STREAM 0x454d4954u /* "EMIT" */
+/* Append-only: struct_size is set by the caller; fields beyond it read as 0. */
+typedef struct msv_emit_options {
+    uint64_t struct_size;
+    uint64_t length;          /* Lc, as given when length_set (0 is legal), else 400                        */
+    uint64_t max_length;      /* 0 = the default, 2^20; at most 2^31 - 1                                    */
+    int32_t length_set;
+    int32_t unihit;           /* 0 multihit, 1 unihit                                                       */
+    int32_t insert_mode;      /* msv_insert_mode                                                            */
+    int32_t reserved;
+} msv_emit_options;
+/* The record the scan launch writes and the host reads back. */
+typedef struct msv_emit_totals {
+    uint64_t residues, domains, ops, truncated;
+    uint64_t overflow;        /* bit 0 residues, 1 domains, 2 ops: that total exceeds its capacity         */
+} msv_emit_totals;
+/* The truth buffers of a device call (device pointers; capacities in elements). */
+typedef struct msv_emit_truth {
+    uint64_t* d_domain_offsets;   /* [n + 1]                                                                */
+    msv_vit_domain* d_domains;    /* seq = index within the call, ops_begin into d_ops                      */
+    uint64_t domains_capacity;
+    uint8_t* d_ops;
+    uint64_t ops_capacity;
+    uint8_t* d_truncated;         /* [n] 0 / 1                                                              */
+} msv_emit_truth;
+typedef struct msv_emit_result msv_emit_result;
+typedef struct msv_emit_profile msv_emit_profile;
+
+/* Host-only.  The integer tables: background[19], match[model_length][19] and insert[model_length][19] (row 0 and,
+ * for the inserts, every row outside 1 .. LENG-1 are zeros; under MSV_INSERTS_ZERO the insert rows repeat the
+ * background's), transitions[model_length][4] = (T_MM, T_MM+MI, T_IM, T_DM) of nodes 1 .. LENG-1 (zeros elsewhere),
+ * specials[2] = (T_loop, T_J; T_J = 0 for unihit).  Any output may be NULL. */
+msv_status msv_emit_tables(const msv_hmm* hmm, const msv_emit_options* options, uint32_t* background, uint32_t* match,
+                           uint32_t* insert, uint32_t* transitions, uint32_t* specials);
+/* THE definition: sequences first .. first + n - 1 under `seed`. */
+msv_status msv_emit_generate(const msv_hmm* hmm, const msv_emit_options* options, uint64_t seed, uint64_t first,
+                             uint64_t n, msv_emit_result** result);
+uint64_t msv_emit_result_count(const msv_emit_result* result);     /* sequences */
+uint64_t msv_emit_result_residues(const msv_emit_result* result);
+uint64_t msv_emit_result_domains(const msv_emit_result* result);
+uint64_t msv_emit_result_ops(const msv_emit_result* result);
+uint64_t msv_emit_result_chunks(const msv_emit_result* result);    /* device chunks (0 for the host definition) */
+/* codes[residues], offsets[count + 1], domain_offsets[count + 1], domains[] (seq = index in the result), ops[],
+ * truncated[count]; any may be NULL.  A result made without truth has no domains and no ops. */
+msv_status msv_emit_result_copy(const msv_emit_result* result, uint8_t* codes, uint64_t* offsets,
+                                uint64_t* domain_offsets, msv_vit_domain* domains, uint8_t* ops, uint8_t* truncated);
+void msv_emit_result_free(msv_emit_result* result);
+/* The score in nats (float64 sums of the engines' float32 tables, msv_hmm_viterbi_scores' layout; insert_scores NULL =
+ * zeros) of the given true path of one sequence of L residues under msv_sequence_transitions(L): every residue
+ * outside the domains costs tr_loop, N -> B, every J -> B and the final C move cost tr_move, every domain tr_B_Mk,
+ * its emissions and transitions (the exit is free) and tr_E_J (tr_E_C for the last).  -inf for a path without
+ * domains (the scoring model has none); MSV_ERR_INVALID_ARGUMENT for ops that do not replay from (i_from, k_from)
+ * to (i_to, k_to) inside the sequence and the model, or domains that overlap. */
+msv_status msv_emit_path_score(const float* match_scores, const float* insert_scores, const float* transition_scores,
+                               uint32_t model_length, float tr_B_Mk, float tr_E_C, float tr_E_J, const uint8_t* codes,
+                               uint64_t L, const msv_vit_domain* domains, uint32_t n_domains, const uint8_t* ops,
+                               double* score);
+/* Device bytes of one chunk of n sequences holding these totals (msv_emit_batch's workspace arithmetic): 16 n bytes
+ * of counts, n + 1 offsets, then -- with truth -- n + 1 domain offsets and n flags, then the codes, the domains and
+ * the ops, each part rounded up to 16 bytes. */
+uint64_t msv_emit_workspace_bytes(uint64_t n, uint64_t residues, uint64_t domains, uint64_t ops, int truth);
+
+/* The device handle: the threshold tables, uploaded once (under 400 KiB at LENG 2,432; read-only, L2-resident).
+ * Threading as msv_profile: one host thread at a time. */
+msv_status msv_emit_profile_create(int device, const msv_hmm* hmm, const msv_emit_options* options,
+                                   msv_emit_profile** out);
+void msv_emit_profile_destroy(msv_emit_profile* profile);
+/* The working stream of msv_emit_batch where its `stream` is NULL (NULL unbinds: the handle's own stream). */
+msv_status msv_emit_profile_bind_stream(msv_emit_profile* profile, void* stream);
+/* One call, three launches on `stream` (a hipStream_t; not NULL), then the stream is waited for and *totals (may be
+ * NULL) read back.  Count: one sequence per thread walks and writes (length, domains, ops, truncated).  Scan: one
+ * workgroup turns the counts into the n + 1 uint64 offsets at d_offsets (and truth->d_domain_offsets) and writes the
+ * totals record.  Place: the same walk with the same counters stores the codes (and domains, ops, flags).  A total
+ * above its capacity: MSV_ERR_OUT_OF_MEMORY, and neither the scan nor the place launch writes any caller buffer.
+ * truth NULL: only codes and offsets.  d_codes with room for `capacity` bytes; a call addresses fewer than 2^32 - 2^20
+ * residue bytes (else MSV_ERR_OUT_OF_MEMORY, as a capacity).  The batch is usable by msv_score_batch_device,
+ * msv_vit_*, msv_fwd_* and msv_bf_* device calls as it is. */
+msv_status msv_emit_batch_device(msv_emit_profile* profile, uint64_t seed, uint64_t first, uint64_t n,
+                                 uint8_t* d_codes, uint64_t capacity, uint64_t* d_offsets,
+                                 const msv_emit_truth* truth, msv_emit_totals* totals, void* stream);
+/* Host result of sequences first .. first + n - 1, in chunks that fit workspace_bytes (0 = 256 MiB) by
+ * msv_emit_workspace_bytes: a chunk is counted and scanned, halved until it fits (a single sequence that does not:
+ * MSV_ERR_OUT_OF_MEMORY), placed and downloaded.  The bytes do not depend on the chunking. */
+msv_status msv_emit_batch(msv_emit_profile* profile, uint64_t seed, uint64_t first, uint64_t n, int truth,
+                          uint64_t workspace_bytes, void* stream, msv_emit_result** result);
+/* Device times (ms, HIP events around the launches) of the last msv_emit_batch_device or msv_emit_batch call of this
+ * handle: the count, the scan and the place launch, each summed over the call's chunks and retries.  Each interval is
+ * between an event recorded directly before the launch and one directly after it, so it is that kernel's time and
+ * holds no copy, allocation or host wait.  Any may be NULL. */
+msv_status msv_emit_profile_times(const msv_emit_profile* profile, float* count_ms, float* scan_ms, float* place_ms);
+/* Append-only, struct_size set by the caller. */
+typedef struct msv_emit_info {
+    uint32_t struct_size;
+    uint32_t model_length;
+    uint32_t block;                 /* threads per workgroup of the walk kernels                            */
+    uint32_t scan_block;
+    uint32_t count_vgprs, place_vgprs, scan_vgprs;
+    uint32_t count_scratch_bytes, place_scratch_bytes, scan_scratch_bytes;
+    uint32_t count_lds_bytes, place_lds_bytes, scan_lds_bytes;
+    int device;
+    uint64_t table_bytes;
+    uint64_t length, max_length;
+    int32_t unihit, insert_mode;
+    uint64_t default_workspace_bytes;
+} msv_emit_info;
+msv_status msv_emit_describe(const msv_emit_profile* profile, msv_emit_info* out);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

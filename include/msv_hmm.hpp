@@ -409,3 +409,79 @@ inline Calibration calibrate(const std::string& file_path, MSV_HMM* msv_engine, 
     if (s != MSV_OK) throw msv_error(s, std::string("msv_cal_calibrate: ") + msv_status_string(s));
     return c;
 }
+
+// The emit stage (msv.h "Emit stage"): sequences drawn from a profile, this library's own scoring model
+// run forwards, with the true path of each.  cpu_emit is the definition (msv_emit_generate); emit the gfx950 kernels
+// (msv_emit_batch), byte for byte the same.  Header-only: every method is a few C-ABI calls.
+struct Emitted {
+    Packed_sequences sequences;
+    std::vector<uint8_t> truncated;
+    Viterbi_traces truth;  // domains and ops of every sequence; scores are left empty (msv_emit_path_score gives one)
+    uint64_t chunks = 0;
+};
+class Emit_HMM {
+  public:
+    explicit Emit_HMM(const std::string& file_path, const msv_emit_options* options = nullptr, int device = 0) {
+        msv_status s = msv_hmm_read(file_path.c_str(), &hmm_);
+        if (s != MSV_OK) throw msv_error(s, std::string(msv_status_string(s)) + ": " + file_path);
+        if (options) {
+            options_ = *options;
+            has_options_ = true;
+        }
+        s = msv_emit_profile_create(device, hmm_, has_options_ ? &options_ : nullptr, &profile_);
+        if (s != MSV_OK) {
+            msv_hmm_destroy(hmm_);
+            throw msv_error(s, std::string("msv_emit_profile_create: ") + msv_status_string(s));
+        }
+    }
+    ~Emit_HMM() {
+        msv_emit_profile_destroy(profile_);
+        msv_hmm_destroy(hmm_);
+    }
+    Emit_HMM(const Emit_HMM&) = delete;
+    Emit_HMM& operator=(const Emit_HMM&) = delete;
+
+    Emitted cpu_emit(uint64_t n, uint64_t seed = 42, uint64_t first = 0) const {
+        msv_emit_result* r = nullptr;
+        check(msv_emit_generate(hmm_, has_options_ ? &options_ : nullptr, seed, first, n, &r), "msv_emit_generate");
+        return take(r);
+    }
+    // workspace_bytes 0 = the default (256 MiB); the bytes do not depend on it
+    Emitted emit(uint64_t n, uint64_t seed = 42, uint64_t first = 0, bool truth = true, uint64_t workspace_bytes = 0) {
+        msv_emit_result* r = nullptr;
+        check(msv_emit_batch(profile_, seed, first, n, truth ? 1 : 0, workspace_bytes, nullptr, &r), "msv_emit_batch");
+        return take(r);
+    }
+    msv_emit_info describe() const {
+        msv_emit_info info{};
+        info.struct_size = sizeof(info);
+        check(msv_emit_describe(profile_, &info), "msv_emit_describe");
+        return info;
+    }
+    msv_emit_profile* handle() { return profile_; }
+
+  private:
+    static void check(msv_status s, const char* what) {
+        if (s != MSV_OK) throw msv_error(s, std::string(what) + ": " + msv_status_string(s));
+    }
+    static Emitted take(msv_emit_result* r) {
+        Emitted e;
+        e.sequences.codes.resize(msv_emit_result_residues(r));
+        e.sequences.offsets.resize(msv_emit_result_count(r) + 1);
+        e.truncated.resize(msv_emit_result_count(r));
+        e.truth.domain_offsets.resize(msv_emit_result_count(r) + 1);
+        e.truth.domains.resize(msv_emit_result_domains(r));
+        e.truth.ops.resize(msv_emit_result_ops(r));
+        e.chunks = msv_emit_result_chunks(r);
+        const msv_status s =
+            msv_emit_result_copy(r, e.sequences.codes.data(), e.sequences.offsets.data(), e.truth.domain_offsets.data(),
+                                 e.truth.domains.data(), e.truth.ops.data(), e.truncated.data());
+        msv_emit_result_free(r);
+        check(s, "msv_emit_result_copy");
+        return e;
+    }
+    msv_hmm* hmm_ = nullptr;
+    msv_emit_options options_{};
+    bool has_options_ = false;
+    msv_emit_profile* profile_ = nullptr;
+};
