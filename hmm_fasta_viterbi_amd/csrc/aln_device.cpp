@@ -2,17 +2,20 @@
 //
 // The stage runs on a msv_dom_profile (dom_profile.h): the recording and the Backward kernel of aln_kernel.hip read
 // the tables the domain stage's variant installed, the fill kernel a small table of gate bytes made per call.  The
-// host packs the items' residues into a CSR batch of their own (item q is sequence q of it), cuts the items into
-// chunks that fit the workspace as the Viterbi trace's are cut, and runs five launches per chunk, each on its own
-// launch slot: recording Forward, Backward with the combine, OA fill, walk count, walk place.  With the null2 option
-//  two more, plain launches of aln_null2.hip that only read the workspace, after the count walk: the
-// row-block partial sums into a slab buffer of the call's own, then one wave per item that finishes null2[20].
+// item checks, the items' residues packed into a CSR batch of their own (item q is sequence q of it) and the chunks
+// that fit the workspace are item_plan.h's, shared with the split stage; this file allocates the result, adds the
+// null2 unit lists and runs five launches per chunk, the first three each on its own launch slot (stagedev::run with
+// the kernel's own grid): recording Forward, Backward with the combine, OA fill, walk count, walk place.  With the
+// null2 option two more, plain launches of aln_null2.hip that only read the workspace, after the count
+// walk: the row-block partial sums into a slab buffer of the call's own, then one wave per item that finishes
+// null2[20].
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -21,6 +24,7 @@
 #include "aln_null2.h"
 #include "dom_profile.h"
 #include "hip_rt.h"
+#include "host_cpu.h"
 #include "msv.h"
 #include "msv_kernel.h"
 #include "null2_host.h"
@@ -50,45 +54,25 @@ struct msv_aln_result {
 
 namespace {
 
-constexpr uint64_t kDefaultWorkspace = 1ull << 30;
+using itemplan::kDefaultWorkspace;
+using msv_host::read_sized;
+using msv_host::write_sized;
+using msvrt::elapsed;
+using msvrt::fill_nan;
+using msvrt::kernel_footprint;
+using msvrt::upload;
 
 const alnk::AlnVariant* variant_of(const msv_dom_profile* p) {
-    int n = 0;
-    const alnk::AlnVariant* all = alnk::aln_variants(&n);
-    for (int i = 0; i < n; ++i)
-        if (all[i].S == p->v->S && all[i].isc == p->v->isc) return &all[i];
-    return nullptr;
-}
-
-uint32_t full_grid(int device, const void* fn, int waves) {
-    int blocks = 0;
-    (void)msvrt::resident_blocks(device, fn, waves * 64, &blocks);
-    return static_cast<uint32_t>(std::max(1, blocks));
+    return stagedev::find_by_shape(alnk::aln_variants, p->v->S, p->v->isc);
 }
 
 // One persistent launch on the next launch slot over `items` list entries, `waves` of them a workgroup.
 msv_status run_kernel(msv_dom_profile* p, const void* fn, int waves, hipStream_t st, uint64_t items, alnk::AlnArgs& a) {
-    if (items == 0) return MSV_OK;
-    const uint64_t need = (items + static_cast<uint64_t>(waves) - 1) / static_cast<uint64_t>(waves);
-    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(full_grid(p->device, fn, waves), need));
-    MSV_HIP(p->kernels.run(st, stagedev::lazy(p, st), p->d_words.get(), 2, [&](uint32_t* counter) {
-        a.counter = counter;
-        return alnk::aln_launch(fn, waves, blocks, a, st);
-    }));
-    return MSV_OK;
-}
-
-float elapsed(const msvrt::Event& a, const msvrt::Event& b) {
-    float ms = 0.0f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;
-}
-
-template <class T>
-hipError_t upload(DeviceBuffer<T>& d, const std::vector<T>& h, hipStream_t st) {
-    hipError_t e = d.reserve(h.size());
-    if (e == hipSuccess && !h.empty())
-        e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st);
-    return e;
+    return stagedev::run(p, st, items, static_cast<uint64_t>(waves), msvrt::full_grid(p->device, fn, waves * 64),
+                         [&](uint32_t blocks, uint32_t* counter) {
+                             a.counter = counter;
+                             return alnk::aln_launch(fn, waves, blocks, a, st);
+                         });
 }
 
 msv_status align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
@@ -96,28 +80,17 @@ msv_status align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64
                        bool null2, msv_aln_result** result) {
     if (!p || !result || (n && !offsets) || (m && !items)) return MSV_ERR_INVALID_ARGUMENT;
     *result = nullptr;
-    if (n >= (1ull << 32) || m >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
-    uint64_t longest = 0, total = 0;
-    msv_status s = n ? msvrt::csr_extent(offsets, n, &longest, &total) : MSV_OK;
+    uint64_t longest = 0;
+    msv_status s = itemplan::check_items(residues, offsets, n, items, m, &longest);
     if (s != MSV_OK) return s;
-    if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
-    if (longest >= (1ull << 31)) return MSV_ERR_SEQUENCE_TOO_LONG;
-    for (uint64_t q = 0; q < m; ++q) {
-        const msv_aln_item& it = items[q];
-        if (it.seq >= n || it.i_from < 1 || it.i_from > it.i_to || it.i_to > offsets[it.seq + 1] - offsets[it.seq])
-            return MSV_ERR_INVALID_ARGUMENT;
-    }
     const alnk::AlnVariant* v = variant_of(p);
     if (!v) return MSV_ERR_UNSUPPORTED_MODEL;
     const uint64_t S = static_cast<uint64_t>(v->S);
     const uint32_t M = p->model_length, K = M - 1;
 
-    auto* r = new (std::nothrow) msv_aln_result;
+    std::unique_ptr<msv_aln_result> guard(new (std::nothrow) msv_aln_result);
+    msv_aln_result* const r = guard.get();
     if (!r) return MSV_ERR_OUT_OF_MEMORY;
-    struct Guard {
-        msv_aln_result* r;
-        ~Guard() { delete r; }
-    } guard{r};
     r->M = M;
     r->kept = keep_posteriors != 0;
     r->has_null2 = null2;
@@ -132,42 +105,20 @@ msv_status align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64
         r->pm.resize(m), r->pi.resize(m), r->pn.resize(m), r->pj.resize(m), r->pc.resize(m);
     }
     auto give = [&](msv_status st) {
-        *result = r;
-        guard.r = nullptr;
+        *result = guard.release();
         return st;
     };
     if (m == 0) return give(MSV_OK);
 
-    // the items as a batch of their own, and the chunks, before anything is launched
-    const uint64_t budget = workspace_bytes ? workspace_bytes : kDefaultWorkspace;
-    std::vector<uint64_t> poff(m + 1, 0), bytes(m), cuts(m + 1, 0), base(m);
-    std::vector<uint32_t> lc(m), sel(m);
-    for (uint64_t q = 0; q < m; ++q) {
-        const uint64_t Le = items[q].i_to - items[q].i_from + 1;
-        poff[q + 1] = poff[q] + Le;
-        bytes[q] = msv_host::aln_item_bytes(S, Le);
-        lc[q] = static_cast<uint32_t>(offsets[items[q].seq + 1] - offsets[items[q].seq]);
-        sel[q] = static_cast<uint32_t>(q);
-    }
-    uint64_t n_chunks = 0;
-    s = msv_vit_trace_chunk_cuts(bytes.data(), m, budget, cuts.data(), &n_chunks);
-    if (s == MSV_ERR_OUT_OF_MEMORY) return give(s);  // (nothing launched: the result says so, chunks = 0)
-    if (s != MSV_OK) return s;
-    std::vector<uint8_t> packed(poff[m]);
-    for (uint64_t q = 0; q < m; ++q)
-        std::copy_n(residues + offsets[items[q].seq] + items[q].i_from - 1, poff[q + 1] - poff[q],
-                    packed.begin() + static_cast<std::ptrdiff_t>(poff[q]));
-    uint64_t chunk_words = 0;
-    std::vector<uint32_t> counts(n_chunks);
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-        uint64_t at = 0;
-        for (uint64_t q = cuts[c]; q < cuts[c + 1]; ++q) {
-            base[q] = at;
-            at += bytes[q] / 4;
-        }
-        chunk_words = std::max(chunk_words, at);
-        counts[c] = static_cast<uint32_t>(cuts[c + 1] - cuts[c]);
-    }
+    // the items as a batch of their own, and the chunks, before anything is launched (item_plan.h)
+    itemplan::ItemBatch plan;
+    if (!itemplan::plan_items(residues, offsets, items, m, workspace_bytes,
+                              [S](uint64_t Le) { return msv_host::aln_item_bytes(S, Le); }, &plan))
+        return give(MSV_ERR_OUT_OF_MEMORY);  // (nothing launched: the result says so, chunks = 0)
+    const std::vector<uint64_t>&poff = plan.poff, &bytes = plan.bytes, &cuts = plan.lay.cuts, &base = plan.lay.base;
+    const std::vector<uint32_t>&lc = plan.lc, &sel = plan.sel, &counts = plan.lay.counts;
+    const std::vector<uint8_t>& packed = plan.packed;
+    const uint64_t n_chunks = plan.lay.chunks(), chunk_words = plan.lay.chunk_units;
     // null2: the units (item, block of kNull2RowBlock rows) of every chunk, chunk after chunk
     const alnk::Null2Variant* nv = null2 ? alnk::null2_variant(v->S, v->isc) : nullptr;
     if (null2 && !nv) return MSV_ERR_UNSUPPORTED_MODEL;
@@ -219,7 +170,7 @@ msv_status align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64
     MSV_HIP(sg.d_scores.reserve(m));
     MSV_HIP(d_oa.reserve(m));
     MSV_HIP(d_ws.reserve(chunk_words));
-    MSV_HIP(d_wcounts.reserve(2 * static_cast<size_t>(*std::max_element(counts.begin(), counts.end()))));
+    MSV_HIP(d_wcounts.reserve(2 * plan.lay.chunk_entries));
     msvrt::StreamDrain drain(st);
     MSV_HIP(sg.upload(packed.data(), poff.data(), 0, m, true, st, st));
     MSV_HIP(upload(d_lc, lc, st));
@@ -230,8 +181,8 @@ msv_status align_batch(msv_dom_profile* p, const uint8_t* residues, const uint64
     MSV_HIP(d_items.reserve(m));
     MSV_HIP(hipMemcpyAsync(d_items, items, m * sizeof(msv_aln_item), hipMemcpyHostToDevice, st));
     // an item the kernels refuse keeps what is set here: NaN scores
-    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sg.d_scores.get()), 0x7fc00000, m, st));
-    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_oa.get()), 0x7fc00000, m, st));
+    MSV_HIP(fill_nan(sg.d_scores, m, st));
+    MSV_HIP(fill_nan(d_oa, m, st));
     alnk::Null2Args na{};
     if (null2) {
         MSV_HIP(upload(d_unit_item, unit_item, st));
@@ -416,11 +367,7 @@ msv_status msv_aln_align_batch_opts(msv_dom_profile* p, const uint8_t* residues,
                                     const msv_aln_item* items, uint64_t m, const msv_aln_options* options,
                                     msv_aln_result** result) {
     msv_aln_options o;
-    std::memset(&o, 0, sizeof(o));
-    if (options) {
-        if (options->struct_size < sizeof(uint64_t)) return MSV_ERR_INVALID_ARGUMENT;
-        std::memcpy(&o, options, static_cast<size_t>(std::min<uint64_t>(options->struct_size, sizeof(o))));
-    }
+    if (!read_sized(options, &o, sizeof(uint64_t))) return MSV_ERR_INVALID_ARGUMENT;
     return align_batch(p, residues, offsets, n, items, m, o.workspace_bytes, o.keep_posteriors, o.null2 != 0, result);
 }
 
@@ -450,9 +397,7 @@ msv_status msv_aln_result_null2_stats(const msv_aln_result* r, msv_aln_null2_sta
     st.null2_ms = r->null2_ms;
     st.partial_ms = r->null2_partial_ms;
     st.slab_bytes = r->slab_bytes;
-    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(st)));
-    st.struct_size = size;
-    std::memcpy(out, &st, size);
+    write_sized(out, st);
     return MSV_OK;
 }
 
@@ -501,42 +446,21 @@ msv_status msv_aln_describe(const msv_dom_profile* p, msv_aln_info* out) {
     std::memset(&info, 0, sizeof(info));
     info.states_per_lane = static_cast<uint32_t>(v->S);
     info.pointer_words = static_cast<uint32_t>(msv_host::aln_pointer_words(static_cast<uint64_t>(v->S)));
-    info.forward_blocks = full_grid(p->device, v->fwd_fn, v->waves);
-    info.backward_blocks = full_grid(p->device, v->bck_fn, v->waves);
-    info.fill_blocks = full_grid(p->device, v->fill_fn, alnk::kFillWaves);
+    info.forward_blocks = msvrt::full_grid(p->device, v->fwd_fn, v->waves * 64);
+    info.backward_blocks = msvrt::full_grid(p->device, v->bck_fn, v->waves * 64);
+    info.fill_blocks = msvrt::full_grid(p->device, v->fill_fn, alnk::kFillWaves * 64);
     info.default_workspace_bytes = kDefaultWorkspace;
     std::snprintf(info.variant, sizeof(info.variant), "%s", v->name);
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, v->fwd_fn) == hipSuccess) {
-        info.forward_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.forward_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    if (hipFuncGetAttributes(&fa, v->bck_fn) == hipSuccess) {
-        info.backward_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.backward_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    if (hipFuncGetAttributes(&fa, v->fill_fn) == hipSuccess) {
-        info.fill_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.fill_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    if (hipFuncGetAttributes(&fa, alnk::walk_fn()) == hipSuccess) {
-        info.walk_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.walk_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
+    kernel_footprint(v->fwd_fn, &info.forward_scratch_bytes, &info.forward_lds_bytes);
+    kernel_footprint(v->bck_fn, &info.backward_scratch_bytes, &info.backward_lds_bytes);
+    kernel_footprint(v->fill_fn, &info.fill_scratch_bytes, &info.fill_lds_bytes);
+    kernel_footprint(alnk::walk_fn(), &info.walk_scratch_bytes, &info.walk_lds_bytes);
     info.null2_row_block = static_cast<uint32_t>(msv_host::kNull2RowBlock);
     if (const alnk::Null2Variant* nv = alnk::null2_variant(v->S, v->isc)) {
-        if (hipFuncGetAttributes(&fa, nv->partial_fn) == hipSuccess) {
-            info.null2_partial_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-            info.null2_partial_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-        }
-        if (hipFuncGetAttributes(&fa, nv->finish_fn) == hipSuccess) {
-            info.null2_finish_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-            info.null2_finish_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-        }
+        kernel_footprint(nv->partial_fn, &info.null2_partial_scratch_bytes, &info.null2_partial_lds_bytes);
+        kernel_footprint(nv->finish_fn, &info.null2_finish_scratch_bytes, &info.null2_finish_lds_bytes);
     }
-    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(info)));
-    info.struct_size = size;
-    std::memcpy(out, &info, size);
+    write_sized(out, info);
     return MSV_OK;
 }
 

@@ -127,12 +127,7 @@ msv_status msv_bf_profile_describe(const msv_bf_profile* p, msv_bf_info* out) {
     out->device = p->device;
     std::memcpy(out->table, p->table, sizeof(p->table));
     std::snprintf(out->variant, sizeof(out->variant), "bf_c%d_w%d", bfk::kChunk, bfk::kWaves);
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, bfk::bf_kernel()) == hipSuccess) {
-        out->scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        out->lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-        out->vgprs = static_cast<uint32_t>(fa.numRegs);
-    }
+    msvrt::kernel_footprint(bfk::bf_kernel(), &out->scratch_bytes, &out->lds_bytes, &out->vgprs);
     return MSV_OK;
 }
 

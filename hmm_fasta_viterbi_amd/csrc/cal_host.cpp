@@ -34,11 +34,7 @@ uint64_t cal_chunk_sequences(uint64_t budget, uint64_t L) {
 
 bool cal_plan(const msv_cal_options* options, uint32_t sets, CalPlan* plan) {
     msv_cal_options o;
-    std::memset(&o, 0, sizeof(o));
-    if (options) {
-        if (options->struct_size < sizeof(uint64_t)) return false;
-        std::memcpy(&o, options, static_cast<size_t>(std::min<uint64_t>(options->struct_size, sizeof(o))));
-    }
+    if (!read_sized(options, &o, sizeof(uint64_t))) return false;
     for (int s = 0; s < 3; ++s) {
         plan->n[s] = o.n[s] ? o.n[s] : kCalDefaultN[s];
         plan->L[s] = o.length[s] ? o.length[s] : kCalDefaultL[s];
@@ -78,11 +74,7 @@ void cal_finish(const CalPlan& plan, uint32_t sets, double lambda, const msv_cal
     }
     r.seed = plan.seed;
     r.tail = plan.tail;
-    if (report && report->struct_size >= sizeof(uint32_t)) {
-        const uint32_t size = std::min<uint32_t>(report->struct_size, static_cast<uint32_t>(sizeof(r)));
-        r.struct_size = size;
-        std::memcpy(report, &r, size);
-    }
+    if (report && report->struct_size >= sizeof(uint32_t)) write_sized(report, r);
 }
 
 namespace {

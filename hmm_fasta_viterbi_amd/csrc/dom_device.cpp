@@ -3,13 +3,15 @@
 // A msv_dom_profile is a stage profile (stage_profile.h) of one compiled variant of dom_kernel.hip: Forward's odds
 // tables and scan constants for the recording kernel, the own-node transition arrays and the mirrored scan constants
 // for the Backward kernel.  A decode is two persistent launches per chunk of selected sequences (each on its own
-// launch slot), the chunks cut to the workspace as the Viterbi trace's are; the envelope rule follows on the device.
+// launch slot), the chunks laid out in record rows by item_plan.h's chunk_layout; the envelope rule follows on the
+// device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -17,6 +19,7 @@
 #include "dom_kernel.h"
 #include "dom_profile.h"
 #include "hip_rt.h"
+#include "host_cpu.h"
 #include "msv.h"
 #include "msv_kernel.h"
 #include "stage_profile.h"
@@ -37,7 +40,8 @@ struct msv_dom_result {
 
 namespace {
 
-constexpr uint64_t kDefaultWorkspace = 1ull << 30;
+using msvrt::elapsed;
+using msvrt::fill_nan;
 
 float odds(float log_score) { return static_cast<float>(std::exp(static_cast<double>(log_score))); }
 
@@ -97,20 +101,15 @@ domk::DomArgs batch_args(msv_dom_profile* p, const uint8_t* d_residues, const ui
     return a;
 }
 
-// One persistent launch on the next launch slot, over at most `items` list entries (stagedev::run with the grid of
-// the kernel at hand).
-msv_status run_kernel(msv_dom_profile* p, const void* fn, uint32_t full_grid, hipStream_t st, uint64_t items,
+// One persistent launch on the next launch slot, over at most `items` list entries, with the grid of the kernel at
+// hand.
+msv_status run_kernel(msv_dom_profile* p, const void* fn, uint32_t grid, hipStream_t st, uint64_t items,
                       domk::DomArgs& a) {
-    if (items == 0) return MSV_OK;
-    if (items >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
-    const uint64_t per_block = static_cast<uint64_t>(p->v->waves);
-    const uint64_t need = (items + per_block - 1) / per_block;
-    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(full_grid, need));
-    MSV_HIP(p->kernels.run(st, stagedev::lazy(p, st), p->d_words.get(), 2, [&](uint32_t* counter) {
-        a.counter = counter;
-        return domk::dom_launch(fn, p->v->waves, blocks, a, st);
-    }));
-    return MSV_OK;
+    return stagedev::run(p, st, items, static_cast<uint64_t>(p->v->waves), grid,
+                         [&](uint32_t blocks, uint32_t* counter) {
+                             a.counter = counter;
+                             return domk::dom_launch(fn, p->v->waves, blocks, a, st);
+                         });
 }
 
 // The recording launch (records null: the Forward score alone).
@@ -143,11 +142,6 @@ msv_status launch(msv_dom_profile* p, const uint8_t* d_residues, const uint64_t*
     Outputs o;
     o.fwd = d_scores;
     return launch_forward(p, batch_args(p, d_residues, d_offsets, n, d_select, d_select_count, errors), o, n, st);
-}
-
-float elapsed(const msvrt::Event& a, const msvrt::Event& b) {
-    float ms = 0.0f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;
 }
 
 }  // namespace
@@ -207,19 +201,11 @@ msv_status msv_dom_profile_describe(const msv_dom_profile* p, msv_dom_info* out)
     info.max_length = p->lentab_n ? p->lentab_n - 1 : 0;
     info.device = p->device;
     std::snprintf(info.variant, sizeof(info.variant), "%s", p->v->name);
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, p->v->fn) == hipSuccess) {
-        info.scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    if (hipFuncGetAttributes(&fa, p->v->bck_fn) == hipSuccess) {
-        info.scratch_bytes = std::max(info.scratch_bytes, static_cast<uint32_t>(fa.localSizeBytes));
-        info.backward_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    // append-only: no more than the caller's struct is written, and struct_size says how much was
-    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(info)));
-    info.struct_size = size;
-    std::memcpy(out, &info, size);
+    uint32_t bck_scratch = 0;
+    msvrt::kernel_footprint(p->v->fn, &info.scratch_bytes, &info.lds_bytes);
+    msvrt::kernel_footprint(p->v->bck_fn, &bck_scratch, &info.backward_lds_bytes);
+    info.scratch_bytes = std::max(info.scratch_bytes, bck_scratch);
+    msv_host::write_sized(out, info);
     return MSV_OK;
 }
 
@@ -291,37 +277,20 @@ msv_status msv_dom_decode_batch(msv_dom_profile* p, const uint8_t* residues, con
         if (sel[q] >= n) return MSV_ERR_INVALID_ARGUMENT;
     }
     // the chunks, before anything is launched: a sequence that alone exceeds the workspace is refused here
-    const uint64_t budget = workspace_bytes ? workspace_bytes : kDefaultWorkspace;
-    std::vector<uint64_t> bytes(m), cuts(m + 1, 0), rows(m);
+    // (a list with repeats may be longer than the batch, a launch's list may not, seq_queue.h: no chunk over n)
+    constexpr uint64_t kRowBytes = domk::kRowWords * sizeof(uint32_t);
+    std::vector<uint64_t> bytes(m);
     for (uint64_t q = 0; q < m; ++q) bytes[q] = msv_host::dom_sequence_bytes(offsets[sel[q] + 1] - offsets[sel[q]]);
-    uint64_t n_chunks = 0;
-    if (m && (s = msv_vit_trace_chunk_cuts(bytes.data(), m, budget, cuts.data(), &n_chunks)) != MSV_OK) return s;
-    if (m > n) {
-        // a list with repeats may be longer than the batch, a launch's list may not (seq_queue.h): cut again
-        std::vector<uint64_t> fine{0};
-        for (uint64_t c = 0; c < n_chunks; ++c)
-            for (uint64_t lo = cuts[c]; lo < cuts[c + 1]; lo += n) fine.push_back(std::min(lo + n, cuts[c + 1]));
-        cuts = fine;
-        n_chunks = cuts.size() - 1;
-    }
-    uint64_t chunk_rows = 0, record_bytes = 0;
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-        uint64_t at = 0;
-        for (uint64_t q = cuts[c]; q < cuts[c + 1]; ++q) {
-            rows[q] = at;
-            at += bytes[q] / (domk::kRowWords * sizeof(uint32_t));
-        }
-        chunk_rows = std::max(chunk_rows, at);
-        record_bytes += at * domk::kRowWords * sizeof(uint32_t);
-    }
-    auto* r = new (std::nothrow) msv_dom_result;
+    itemplan::ChunkLayout lay;  // in record rows
+    if (!itemplan::chunk_layout(bytes.data(), m, workspace_bytes, kRowBytes, n, &lay)) return MSV_ERR_OUT_OF_MEMORY;
+    const std::vector<uint64_t>&cuts = lay.cuts, &rows = lay.base;
+    const std::vector<uint32_t>& counts = lay.counts;
+    const uint64_t n_chunks = lay.chunks();
+    std::unique_ptr<msv_dom_result> guard(new (std::nothrow) msv_dom_result);
+    msv_dom_result* const r = guard.get();
     if (!r) return MSV_ERR_OUT_OF_MEMORY;
-    struct Guard {
-        msv_dom_result* r;
-        ~Guard() { delete r; }
-    } guard{r};
     r->stats.chunks = n_chunks;
-    r->stats.record_bytes = record_bytes;
+    r->stats.record_bytes = lay.total_units * kRowBytes;
     r->fwd.assign(m, 0.0f);
     r->bck.assign(m, 0.0f);
     r->res_off.assign(m + 1, 0);
@@ -331,8 +300,7 @@ msv_status msv_dom_decode_batch(msv_dom_profile* p, const uint8_t* residues, con
     r->end.assign(r->res_off[m], 0.0f);
     r->occ.assign(r->res_off[m], 0.0f);
     if (m == 0) {
-        *result = r;
-        guard.r = nullptr;
+        *result = guard.release();
         return MSV_OK;
     }
 
@@ -341,14 +309,12 @@ msv_status msv_dom_decode_batch(msv_dom_profile* p, const uint8_t* residues, con
     if ((s = msv_dom_profile_reserve_length(p, longest)) != MSV_OK) return s;
     hipStream_t st = p->stream;
     msvrt::CsrStaging& sg = p->staged;
-    std::vector<uint32_t> counts(n_chunks);
-    for (uint64_t c = 0; c < n_chunks; ++c) counts[c] = static_cast<uint32_t>(cuts[c + 1] - cuts[c]);
     MSV_HIP(sg.d_scores.reserve(n));
     MSV_HIP(p->d_bck.reserve(n));
     MSV_HIP(p->d_begin.reserve(total));
     MSV_HIP(p->d_end.reserve(total));
     MSV_HIP(p->d_occ.reserve(total));
-    MSV_HIP(p->d_records.reserve(chunk_rows * domk::kRowWords));
+    MSV_HIP(p->d_records.reserve(lay.chunk_units * domk::kRowWords));
     MSV_HIP(p->d_sel.reserve(m));
     MSV_HIP(p->d_rows.reserve(m));
     MSV_HIP(p->d_counts.reserve(n_chunks));
@@ -362,8 +328,8 @@ msv_status msv_dom_decode_batch(msv_dom_profile* p, const uint8_t* residues, con
     MSV_HIP(hipMemcpyAsync(p->d_rows, rows.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     MSV_HIP(hipMemcpyAsync(p->d_counts, counts.data(), n_chunks * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     // an entry the kernels refuse keeps what is set here: NaN scores, zero posteriors
-    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sg.d_scores.get()), 0x7fc00000, n, st));
-    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->d_bck.get()), 0x7fc00000, n, st));
+    MSV_HIP(fill_nan(sg.d_scores, n, st));
+    MSV_HIP(fill_nan(p->d_bck, n, st));
     if (total) {
         MSV_HIP(hipMemsetAsync(p->d_begin, 0, total * sizeof(float), st));
         MSV_HIP(hipMemsetAsync(p->d_end, 0, total * sizeof(float), st));
@@ -438,8 +404,7 @@ msv_status msv_dom_decode_batch(msv_dom_profile* p, const uint8_t* residues, con
     }
     s = stagedev::read_errors(p, kHostErrWord, st);
     if (s != MSV_OK && s != MSV_ERR_BAD_RESIDUE && s != MSV_ERR_SEQUENCE_TOO_LONG) return s;
-    *result = r;
-    guard.r = nullptr;
+    *result = guard.release();
     return s;
 }
 

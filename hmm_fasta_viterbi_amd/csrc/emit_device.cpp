@@ -9,11 +9,13 @@
 #include <algorithm>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 
 #include "emit_host.h"
 #include "emit_kernel.h"
 #include "hip_rt.h"
+#include "host_cpu.h"
 #include "msv.h"
 
 using msvrt::DeviceBuffer;
@@ -97,8 +99,7 @@ msv_status enqueue_place(msv_emit_profile* p, uint64_t seed, uint64_t first, uin
 
 // Adds the device time between two recorded events, after the stream is done.
 void add_ms(msv_emit_profile* p, int kind, int from) {
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, p->ev[from], p->ev[from + 1]) == hipSuccess) p->ms[kind] += ms;
+    p->ms[kind] += msvrt::elapsed(p->ev[from], p->ev[from + 1]);
 }
 
 bool truth_ok(const msv_emit_truth* t, uint64_t n) {
@@ -129,11 +130,8 @@ msv_status msv_emit_profile_create(int device, const msv_hmm* hmm, const msv_emi
     if (s != MSV_OK) return s;
     DeviceGuard g(device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
-    auto* p = new msv_emit_profile;
-    struct Guard {
-        msv_emit_profile* p;
-        ~Guard() { delete p; }
-    } guard{p};
+    std::unique_ptr<msv_emit_profile> guard(new msv_emit_profile);
+    msv_emit_profile* const p = guard.get();
     p->device = device;
     p->tables = std::move(tables);
     MSV_HIP(p->d_match.replace_with(p->tables.match.data(), p->tables.match.size()));
@@ -143,8 +141,7 @@ msv_status msv_emit_profile_create(int device, const msv_hmm* hmm, const msv_emi
     MSV_HIP(p->h_record.reserve(1));
     MSV_HIP(p->own.create(hipStreamNonBlocking));
     for (auto& e : p->ev) MSV_HIP(e.create(hipEventDefault));
-    *out = p;
-    guard.p = nullptr;
+    *out = guard.release();
     return MSV_OK;
 } catch (const std::bad_alloc&) {
     return MSV_ERR_OUT_OF_MEMORY;
@@ -199,11 +196,8 @@ msv_status msv_emit_batch(msv_emit_profile* p, uint64_t seed, uint64_t first, ui
                            : p->bound ? p->bound
                                       : static_cast<hipStream_t>(p->own);
 
-    auto* r = new msv_emit_result;
-    struct Guard {
-        msv_emit_result* r;
-        ~Guard() { delete r; }
-    } guard{r};
+    std::unique_ptr<msv_emit_result> guard(new msv_emit_result);
+    msv_emit_result* const r = guard.get();
     r->truth = tr;
     r->offsets.assign(n + 1, 0);
     r->domain_offsets.assign(n + 1, 0);
@@ -280,8 +274,7 @@ msv_status msv_emit_batch(msv_emit_profile* p, uint64_t seed, uint64_t first, ui
         done += m;
     }
     drain.disarm();
-    *result = r;
-    guard.r = nullptr;
+    *result = guard.release();
     return MSV_OK;
 } catch (const std::bad_alloc&) {
     return MSV_ERR_OUT_OF_MEMORY;
@@ -304,22 +297,9 @@ msv_status msv_emit_describe(const msv_emit_profile* p, msv_emit_info* out) {
     info.model_length = p->tables.model_length;
     info.block = emitk::kWalkBlock;
     info.scan_block = emitk::kScanBlock;
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, emitk::count_fn()) == hipSuccess) {
-        info.count_vgprs = static_cast<uint32_t>(fa.numRegs);
-        info.count_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.count_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    if (hipFuncGetAttributes(&fa, emitk::place_fn()) == hipSuccess) {
-        info.place_vgprs = static_cast<uint32_t>(fa.numRegs);
-        info.place_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.place_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    if (hipFuncGetAttributes(&fa, emitk::scan_fn()) == hipSuccess) {
-        info.scan_vgprs = static_cast<uint32_t>(fa.numRegs);
-        info.scan_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.scan_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
+    msvrt::kernel_footprint(emitk::count_fn(), &info.count_scratch_bytes, &info.count_lds_bytes, &info.count_vgprs);
+    msvrt::kernel_footprint(emitk::place_fn(), &info.place_scratch_bytes, &info.place_lds_bytes, &info.place_vgprs);
+    msvrt::kernel_footprint(emitk::scan_fn(), &info.scan_scratch_bytes, &info.scan_lds_bytes, &info.scan_vgprs);
     info.device = p->device;
     info.table_bytes = p->tables.bytes();
     info.length = p->tables.length;
@@ -327,9 +307,7 @@ msv_status msv_emit_describe(const msv_emit_profile* p, msv_emit_info* out) {
     info.unihit = p->tables.config.multihit ? 0 : 1;
     info.insert_mode = p->tables.config.file_inserts ? MSV_INSERTS_LOG_ODDS : MSV_INSERTS_ZERO;
     info.default_workspace_bytes = msv_host::kEmitDefaultWorkspace;
-    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(info)));
-    info.struct_size = size;
-    std::memcpy(out, &info, size);
+    msv_host::write_sized(out, info);
     return MSV_OK;
 }
 

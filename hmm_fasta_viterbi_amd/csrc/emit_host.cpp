@@ -5,7 +5,10 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
+
+#include "host_cpu.h"
 
 namespace msv_host {
 
@@ -54,11 +57,7 @@ struct VectorSink {
 msv_status emit_tables(const msv_hmm* hmm, const msv_emit_options* options, EmitTables* out) {
     if (!hmm || !out) return MSV_ERR_INVALID_ARGUMENT;
     msv_emit_options o;
-    std::memset(&o, 0, sizeof(o));
-    if (options) {
-        if (options->struct_size < sizeof(uint64_t)) return MSV_ERR_INVALID_ARGUMENT;
-        std::memcpy(&o, options, static_cast<size_t>(std::min<uint64_t>(options->struct_size, sizeof(o))));
-    }
+    if (!read_sized(options, &o, sizeof(uint64_t))) return MSV_ERR_INVALID_ARGUMENT;
     const uint64_t Lc = o.length_set ? o.length : kEmitDefaultLength;
     const uint64_t max_length = o.max_length ? o.max_length : kEmitDefaultMaxLength;
     if (Lc >= (1ull << 40) || max_length >= (1ull << 31) || (o.unihit != 0 && o.unihit != 1) ||
@@ -142,11 +141,8 @@ msv_status msv_emit_generate(const msv_hmm* hmm, const msv_emit_options* options
     EmitTables t;
     const msv_status s = emit_tables(hmm, options, &t);
     if (s != MSV_OK) return s;
-    auto* r = new msv_emit_result;
-    struct Guard {
-        msv_emit_result* r;
-        ~Guard() { delete r; }
-    } guard{r};
+    std::unique_ptr<msv_emit_result> guard(new msv_emit_result);
+    msv_emit_result* const r = guard.get();
     r->offsets.assign(n + 1, 0);
     r->domain_offsets.assign(n + 1, 0);
     r->truncated.assign(n, 0);
@@ -158,8 +154,7 @@ msv_status msv_emit_generate(const msv_hmm* hmm, const msv_emit_options* options
         r->offsets[j + 1] = r->codes.size();
         r->domain_offsets[j + 1] = r->domains.size();
     }
-    *result = r;
-    guard.r = nullptr;
+    *result = guard.release();
     return MSV_OK;
 } catch (const std::bad_alloc&) {
     return MSV_ERR_OUT_OF_MEMORY;

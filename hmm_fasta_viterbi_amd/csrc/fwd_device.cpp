@@ -140,11 +140,7 @@ msv_status msv_fwd_profile_describe(const msv_fwd_profile* p, msv_fwd_info* out)
     out->max_length = p->lentab_n ? p->lentab_n - 1 : 0;
     out->device = p->device;
     std::snprintf(out->variant, sizeof(out->variant), "%s", p->v->name);
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, p->v->fn) == hipSuccess) {
-        out->scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        out->lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
+    msvrt::kernel_footprint(p->v->fn, &out->scratch_bytes, &out->lds_bytes);
     return MSV_OK;
 }
 

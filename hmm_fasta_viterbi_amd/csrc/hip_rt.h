@@ -1,7 +1,9 @@
 // hip_rt.h -- the host device layer's HIP plumbing, shared by msv_device.cpp, msv_multi.cpp, the host half of
 // fasta_device.hip and, through stage_profile.h, the Viterbi and Forward layers: the device guard, the status
 // mapping and its return-on-error macro, move-only owners of device buffers, pinned buffers, streams and events,
-// the checks every host entry point opens with, and the staging of one host batch (CsrStaging).
+// the checks every host entry point opens with, the staging of one host batch (CsrStaging), and the few lines every
+// device layer would otherwise spell for itself: a kernel's full grid and footprint, the time between two events, a
+// host list's upload, the NaN pre-fill of scores.
 //
 // The owners never switch devices and never synchronise on their own (the one exception is documented at
 // DeviceBuffer::replace_with): whoever destroys or shrinks one does so with its device current and with
@@ -14,7 +16,9 @@
 #include <cstddef>
 #include <cstdint>
 #include <utility>
+#include <vector>
 
+#include "item_plan.h"
 #include "msv.h"
 #include "msv_plan.h"
 
@@ -63,17 +67,25 @@ inline hipError_t resident_blocks(int device, const void* kernel, int threads, i
     return e;
 }
 
-// Validates a CSR (offsets non-decreasing) and finds its longest sequence and its residue count.
-inline msv_status csr_extent(const uint64_t* offsets, uint64_t n, uint64_t* maxL, uint64_t* total) {
-    uint64_t longest = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-        if (offsets[s + 1] < offsets[s]) return MSV_ERR_INVALID_ARGUMENT;
-        longest = std::max<uint64_t>(longest, offsets[s + 1] - offsets[s]);
-    }
-    *maxL = longest;
-    *total = n ? offsets[n] - offsets[0] : 0;
-    return MSV_OK;
+// resident_blocks for the answers that need a grid whatever the queries say: at least one block.
+inline uint32_t full_grid(int device, const void* kernel, int threads) {
+    int blocks = 0;
+    (void)resident_blocks(device, kernel, threads, &blocks);
+    return static_cast<uint32_t>(std::max(1, blocks));
 }
+
+// What a kernel keeps per thread in scratch and per block in LDS, and its vector registers (left as they are when
+// the query fails).
+inline void kernel_footprint(const void* kernel, uint32_t* scratch, uint32_t* lds, uint32_t* vgprs = nullptr) {
+    hipFuncAttributes fa{};
+    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return;
+    if (scratch) *scratch = static_cast<uint32_t>(fa.localSizeBytes);
+    if (lds) *lds = static_cast<uint32_t>(fa.sharedSizeBytes);
+    if (vgprs) *vgprs = static_cast<uint32_t>(fa.numRegs);
+}
+
+// Validates a CSR (offsets non-decreasing) and finds its longest sequence and its residue count (item_plan.h).
+using itemplan::csr_extent;
 
 // Owner of one allocation of `capacity()` elements: device memory (hipMalloc) or, Pinned, page-locked host
 // memory (hipHostMalloc with the caller's flags).  Converts to the raw pointer.
@@ -162,6 +174,26 @@ private:
 };
 using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
 using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+
+// Milliseconds between two recorded, completed events (0 when the runtime cannot say).
+inline float elapsed(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.0f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;
+}
+
+// Room for a host list on the device and its copy queued on `st` (the list outlives the copy: the caller's).
+template <class T>
+hipError_t upload(DeviceBuffer<T>& d, const std::vector<T>& h, hipStream_t st) {
+    hipError_t e = d.reserve(h.size());
+    if (e == hipSuccess && !h.empty())
+        e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    return e;
+}
+
+// n scores of quiet-NaN bits: what an entry that the kernels refuse keeps.
+inline hipError_t fill_nan(float* d, size_t n, hipStream_t st) {
+    return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), 0x7fc00000, n, st);
+}
 
 // Synchronises up to three streams when a host call returns early: copies that read its pinned staging
 // (rewritten by the next call) and kernels that write its buffers may still be queued.  disarm() on the

@@ -1,13 +1,34 @@
-// host_cpu.h -- host-only internals shared by msv_hmm.cpp and the sanitizer drivers (host_common.cpp).
+// host_cpu.h -- host-only internals shared by msv_hmm.cpp and the sanitizer drivers (host_common.cpp), and the
+// struct_size convention of msv.h's append-only structs for every *_device.cpp and *_host.cpp.
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "msv.h"
 
 namespace msv_host {
+
+// msv.h's append-only structs (struct_size first).  read_sized: *out is zeroed, then the caller's bytes are copied
+// in, no more than either side has (null `in`: all zeros); false where the caller's struct is smaller than min_size.
+template <class T>
+bool read_sized(const T* in, T* out, size_t min_size) {
+    std::memset(out, 0, sizeof(T));
+    if (!in) return true;
+    if (in->struct_size < min_size) return false;
+    std::memcpy(out, in, static_cast<size_t>(std::min<uint64_t>(in->struct_size, sizeof(T))));
+    return true;
+}
+// write_sized: no more than the caller's struct is written, and its struct_size says how much was.
+template <class T>
+void write_sized(T* out, T value) {
+    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(T)));
+    value.struct_size = size;
+    std::memcpy(out, &value, size);
+}
 
 // MSV_HMM::run_on_sequence (MSV_HMM.cpp:74-113) on codes 0..19: emission_scores is the [20][M]
 // residue-major table of MSV_HMM.cpp:38-45 (M = LENG + 1), the score is C_L + tr_move.

@@ -2,21 +2,23 @@
 //
 // The stage runs on a msv_dom_profile as the alignment stage does (aln_device.cpp): the recording kernel of
 // spl_kernel.hip reads the tables the domain stage's variant installed, the sampler a flat table of the float32
-// transition odds made per call.  The host packs the items' residues into a CSR batch of their own (item q is
-// sequence q of it), cuts the items into chunks that fit the workspace as the Viterbi trace's are cut, and runs three
-// launches per chunk: the recording Forward on a launch slot of its own, the sampler's count pass and, after a host
-// scan, its place pass.
+// transition odds made per call.  The item checks, the items' residues packed into a CSR batch of their own (item q
+// is sequence q of it) and the chunks that fit the workspace are item_plan.h's, as the alignment stage's; this file
+// allocates the result and runs three launches per chunk: the recording Forward on a launch slot of its own
+// (stagedev::run with that kernel's grid), the sampler's count pass and, after a host scan, its place pass.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "dom_profile.h"
 #include "hip_rt.h"
+#include "host_cpu.h"
 #include "msv.h"
 #include "msv_kernel.h"
 #include "spl_host.h"
@@ -40,66 +42,34 @@ struct msv_spl_result {
 
 namespace {
 
-constexpr uint64_t kDefaultWorkspace = 1ull << 30;
+using itemplan::kDefaultWorkspace;
+using msv_host::read_sized;
+using msv_host::write_sized;
+using msvrt::elapsed;
+using msvrt::upload;
+
 constexpr uint32_t kDefaultSamples = 200;
 constexpr uint64_t kDefaultSeed = 42;
-
-const splk::SplVariant* variant_of(const msv_dom_profile* p) {
-    int n = 0;
-    const splk::SplVariant* all = splk::spl_variants(&n);
-    for (int i = 0; i < n; ++i)
-        if (all[i].S == p->v->S && all[i].isc == p->v->isc) return &all[i];
-    return nullptr;
-}
-
-uint32_t full_grid(int device, const void* fn, int waves) {
-    int blocks = 0;
-    (void)msvrt::resident_blocks(device, fn, waves * 64, &blocks);
-    return static_cast<uint32_t>(std::max(1, blocks));
-}
-
-float elapsed(const msvrt::Event& a, const msvrt::Event& b) {
-    float ms = 0.0f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;
-}
-
-template <class T>
-hipError_t upload(DeviceBuffer<T>& d, const std::vector<T>& h, hipStream_t st) {
-    hipError_t e = d.reserve(h.size());
-    if (e == hipSuccess && !h.empty())
-        e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st);
-    return e;
-}
 
 msv_status sample_batch(msv_dom_profile* p, const uint8_t* residues, const uint64_t* offsets, uint64_t n,
                         const msv_aln_item* items, uint64_t m, const msv_spl_options& opt, msv_spl_result** result) {
     if (!p || !result || (n && !offsets) || (m && !items)) return MSV_ERR_INVALID_ARGUMENT;
     *result = nullptr;
-    if (n >= (1ull << 32) || m >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
     const uint32_t ns = opt.n_samples ? opt.n_samples : kDefaultSamples;
     const uint64_t seed = opt.seed_set ? opt.seed : kDefaultSeed;
+    // (every refusal up to here and check_items' first is the same status: m * ns may wrap only where m is refused)
     if (ns >= (1u << 24) || m * ns >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
-    uint64_t longest = 0, total = 0;
-    msv_status s = n ? msvrt::csr_extent(offsets, n, &longest, &total) : MSV_OK;
+    uint64_t longest = 0;
+    msv_status s = itemplan::check_items(residues, offsets, n, items, m, &longest);
     if (s != MSV_OK) return s;
-    if (total && !residues) return MSV_ERR_INVALID_ARGUMENT;
-    if (longest >= (1ull << 31)) return MSV_ERR_SEQUENCE_TOO_LONG;
-    for (uint64_t q = 0; q < m; ++q) {
-        const msv_aln_item& it = items[q];
-        if (it.seq >= n || it.i_from < 1 || it.i_from > it.i_to || it.i_to > offsets[it.seq + 1] - offsets[it.seq])
-            return MSV_ERR_INVALID_ARGUMENT;
-    }
-    const splk::SplVariant* v = variant_of(p);
+    const splk::SplVariant* v = stagedev::find_by_shape(splk::spl_variants, p->v->S, p->v->isc);
     if (!v) return MSV_ERR_UNSUPPORTED_MODEL;
     const uint64_t S = static_cast<uint64_t>(v->S);
     const uint32_t M = p->model_length, K = M - 1;
 
-    auto* r = new (std::nothrow) msv_spl_result;
+    std::unique_ptr<msv_spl_result> guard(new (std::nothrow) msv_spl_result);
+    msv_spl_result* const r = guard.get();
     if (!r) return MSV_ERR_OUT_OF_MEMORY;
-    struct Guard {
-        msv_spl_result* r;
-        ~Guard() { delete r; }
-    } guard{r};
     r->M = M;
     r->kept = opt.keep_matrix != 0;
     r->stats.n_samples = ns;
@@ -108,43 +78,18 @@ msv_status sample_batch(msv_dom_profile* p, const uint8_t* residues, const uint6
     r->sample_off.assign(m * ns + 1, 0);
     if (r->kept) r->fm.resize(m), r->fi.resize(m), r->fd.resize(m), r->rec.resize(m);
     auto give = [&](msv_status st) {
-        *result = r;
-        guard.r = nullptr;
+        *result = guard.release();
         return st;
     };
     if (m == 0) return give(MSV_OK);
 
-    // the items as a batch of their own, and the chunks, before anything is launched
-    const uint64_t budget = opt.workspace_bytes ? opt.workspace_bytes : kDefaultWorkspace;
-    std::vector<uint64_t> poff(m + 1, 0), bytes(m), cuts(m + 1, 0), base(m);
-    std::vector<uint32_t> lc(m), sel(m);
-    for (uint64_t q = 0; q < m; ++q) {
-        const uint64_t Le = items[q].i_to - items[q].i_from + 1;
-        poff[q + 1] = poff[q] + Le;
-        bytes[q] = msv_host::spl_item_bytes(S, Le);
-        lc[q] = static_cast<uint32_t>(offsets[items[q].seq + 1] - offsets[items[q].seq]);
-        sel[q] = static_cast<uint32_t>(q);
-    }
-    uint64_t n_chunks = 0;
-    s = msv_vit_trace_chunk_cuts(bytes.data(), m, budget, cuts.data(), &n_chunks);
-    if (s == MSV_ERR_OUT_OF_MEMORY) return give(s);  // (nothing launched: the result says so, chunks = 0)
-    if (s != MSV_OK) return s;
-    std::vector<uint8_t> packed(poff[m]);
-    for (uint64_t q = 0; q < m; ++q)
-        std::copy_n(residues + offsets[items[q].seq] + items[q].i_from - 1, poff[q + 1] - poff[q],
-                    packed.begin() + static_cast<std::ptrdiff_t>(poff[q]));
-    uint64_t chunk_words = 0, chunk_items = 0;
-    std::vector<uint32_t> counts(n_chunks);
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-        uint64_t at = 0;
-        for (uint64_t q = cuts[c]; q < cuts[c + 1]; ++q) {
-            base[q] = at;
-            at += bytes[q] / 4;
-        }
-        chunk_words = std::max(chunk_words, at);
-        counts[c] = static_cast<uint32_t>(cuts[c + 1] - cuts[c]);
-        chunk_items = std::max<uint64_t>(chunk_items, counts[c]);
-    }
+    // the items as a batch of their own, and the chunks, before anything is launched (item_plan.h)
+    itemplan::ItemBatch plan;
+    if (!itemplan::plan_items(residues, offsets, items, m, opt.workspace_bytes,
+                              [S](uint64_t Le) { return msv_host::spl_item_bytes(S, Le); }, &plan))
+        return give(MSV_ERR_OUT_OF_MEMORY);  // (nothing launched: the result says so, chunks = 0)
+    const std::vector<uint64_t>&poff = plan.poff, &bytes = plan.bytes, &cuts = plan.lay.cuts, &base = plan.lay.base;
+    const uint64_t n_chunks = plan.lay.chunks();
 
     DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
@@ -160,19 +105,19 @@ msv_status sample_batch(msv_dom_profile* p, const uint8_t* residues, const uint6
     msvrt::Event ev[5];
     for (auto& e : ev) MSV_HIP(e.create(hipEventDefault));
     MSV_HIP(sg.d_scores.reserve(m));
-    MSV_HIP(d_ws.reserve(chunk_words));
-    MSV_HIP(d_scounts.reserve(chunk_items * ns));
+    MSV_HIP(d_ws.reserve(plan.lay.chunk_units));
+    MSV_HIP(d_scounts.reserve(plan.lay.chunk_entries * ns));
     msvrt::StreamDrain drain(st);
-    MSV_HIP(sg.upload(packed.data(), poff.data(), 0, m, true, st, st));
-    MSV_HIP(upload(d_lc, lc, st));
-    MSV_HIP(upload(d_sel, sel, st));
-    MSV_HIP(upload(d_counts, counts, st));
+    MSV_HIP(sg.upload(plan.packed.data(), poff.data(), 0, m, true, st, st));
+    MSV_HIP(upload(d_lc, plan.lc, st));
+    MSV_HIP(upload(d_sel, plan.sel, st));
+    MSV_HIP(upload(d_counts, plan.lay.counts, st));
     MSV_HIP(upload(d_base, base, st));
     MSV_HIP(upload(d_tr, tr, st));
     MSV_HIP(d_items.reserve(m));
     MSV_HIP(hipMemcpyAsync(d_items, items, m * sizeof(msv_aln_item), hipMemcpyHostToDevice, st));
     // an item the kernel refuses keeps what is set here: a NaN score
-    MSV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sg.d_scores.get()), 0x7fc00000, m, st));
+    MSV_HIP(msvrt::fill_nan(sg.d_scores, m, st));
 
     splk::SplArgs a{};
     a.etab = p->d_etab;
@@ -218,15 +163,13 @@ msv_status sample_batch(msv_dom_profile* p, const uint8_t* residues, const uint6
         a.select = d_sel + lo;
         a.select_count = d_counts + c;
         MSV_HIP(hipEventRecord(ev[0], st));
-        {
-            const uint64_t need = (cnt + static_cast<uint64_t>(v->waves) - 1) / static_cast<uint64_t>(v->waves);
-            const uint32_t blocks =
-                static_cast<uint32_t>(std::min<uint64_t>(full_grid(p->device, v->fwd_fn, v->waves), need));
-            MSV_HIP(p->kernels.run(st, stagedev::lazy(p, st), p->d_words.get(), 2, [&](uint32_t* counter) {
-                a.counter = counter;
-                return splk::spl_launch(v->fwd_fn, v->waves, blocks, a, st);
-            }));
-        }
+        s = stagedev::run(p, st, cnt, static_cast<uint64_t>(v->waves),
+                          msvrt::full_grid(p->device, v->fwd_fn, v->waves * 64),
+                          [&](uint32_t blocks, uint32_t* counter) {
+                              a.counter = counter;
+                              return splk::spl_launch(v->fwd_fn, v->waves, blocks, a, st);
+                          });
+        if (s != MSV_OK) return s;
         MSV_HIP(hipEventRecord(ev[1], st));
         w.lo = static_cast<uint32_t>(lo);
         w.hi = static_cast<uint32_t>(hi);
@@ -305,11 +248,7 @@ msv_status msv_spl_sample_batch(msv_dom_profile* p, const uint8_t* residues, con
                                 const msv_aln_item* items, uint64_t m, const msv_spl_options* options,
                                 msv_spl_result** result) {
     msv_spl_options o;
-    std::memset(&o, 0, sizeof(o));
-    if (options) {
-        if (options->struct_size < sizeof(uint64_t)) return MSV_ERR_INVALID_ARGUMENT;
-        std::memcpy(&o, options, static_cast<size_t>(std::min<uint64_t>(options->struct_size, sizeof(o))));
-    }
+    if (!read_sized(options, &o, sizeof(uint64_t))) return MSV_ERR_INVALID_ARGUMENT;
     return sample_batch(p, residues, offsets, n, items, m, o, result);
 }
 
@@ -337,10 +276,7 @@ msv_status msv_spl_result_matrix(const msv_spl_result* r, uint64_t q, float* fM,
 
 msv_status msv_spl_result_stats(const msv_spl_result* r, msv_spl_stats* out) {
     if (!r || !out || out->struct_size < sizeof(uint32_t)) return MSV_ERR_INVALID_ARGUMENT;
-    msv_spl_stats st = r->stats;
-    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(st)));
-    st.struct_size = size;
-    std::memcpy(out, &st, size);
+    write_sized(out, r->stats);
     return MSV_OK;
 }
 
@@ -348,28 +284,19 @@ void msv_spl_result_free(msv_spl_result* r) { delete r; }
 
 msv_status msv_spl_describe(const msv_dom_profile* p, msv_spl_info* out) {
     if (!p || !out || out->struct_size < sizeof(uint32_t)) return MSV_ERR_INVALID_ARGUMENT;
-    const splk::SplVariant* v = variant_of(p);
+    const splk::SplVariant* v = stagedev::find_by_shape(splk::spl_variants, p->v->S, p->v->isc);
     if (!v) return MSV_ERR_UNSUPPORTED_MODEL;
     DeviceGuard g(p->device);
     if (!g.ok) return MSV_ERR_NO_DEVICE;
     msv_spl_info info;
     std::memset(&info, 0, sizeof(info));
     info.states_per_lane = static_cast<uint32_t>(v->S);
-    info.forward_blocks = full_grid(p->device, v->fwd_fn, v->waves);
+    info.forward_blocks = msvrt::full_grid(p->device, v->fwd_fn, v->waves * 64);
     info.default_workspace_bytes = kDefaultWorkspace;
     std::snprintf(info.variant, sizeof(info.variant), "%s", v->name);
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, v->fwd_fn) == hipSuccess) {
-        info.forward_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.forward_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    if (hipFuncGetAttributes(&fa, splk::sample_fn()) == hipSuccess) {
-        info.sample_scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        info.sample_lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
-    const uint32_t size = std::min<uint32_t>(out->struct_size, static_cast<uint32_t>(sizeof(info)));
-    info.struct_size = size;
-    std::memcpy(out, &info, size);
+    msvrt::kernel_footprint(v->fwd_fn, &info.forward_scratch_bytes, &info.forward_lds_bytes);
+    msvrt::kernel_footprint(splk::sample_fn(), &info.sample_scratch_bytes, &info.sample_lds_bytes);
+    write_sized(out, info);
     return MSV_OK;
 }
 

@@ -9,6 +9,8 @@
 #include <limits>
 #include <numeric>
 
+#include "host_cpu.h"
+
 namespace msv_host {
 
 namespace {
@@ -273,11 +275,7 @@ msv_status msv_spl_cluster(const msv_spl_segment* segments, uint64_t n_segments,
                            msv_spl_envelope* envelopes) {
     if ((n_segments && !segments) || !n_envelopes || n_samples == 0) return MSV_ERR_INVALID_ARGUMENT;
     msv_spl_cluster_options o;
-    std::memset(&o, 0, sizeof(o));
-    if (options) {
-        if (options->struct_size < sizeof(uint64_t)) return MSV_ERR_INVALID_ARGUMENT;
-        std::memcpy(&o, options, static_cast<size_t>(std::min<uint64_t>(options->struct_size, sizeof(o))));
-    }
+    if (!msv_host::read_sized(options, &o, sizeof(uint64_t))) return MSV_ERR_INVALID_ARGUMENT;
     msv_host::SplClusterRule r;
     if (o.min_overlap_den) r.ov_num = o.min_overlap_num, r.ov_den = o.min_overlap_den;
     if (o.max_diagdiff) r.max_diagdiff = o.max_diagdiff;

@@ -5,6 +5,8 @@
 // the device -- is one persistent launch (seq_queue.h is the kernels' side).  msv_vit_profile and msv_fwd_profile
 // derive from StageProfile and add their constants, their variant and their cascade's buffers; the entry points of
 // both are their argument checks and one call into the bodies below, which take what differs as small callables.
+// The domain profile (dom_profile.h) is a third, and the stages that run on it (dom_device.cpp, aln_device.cpp,
+// spl_device.cpp) launch through run() with the grid of the kernel at hand and find their variant by find_by_shape.
 // As hip_rt.h: no virtuals.  (The MSV profile, msv_device.cpp, is another shape: plans, order, chunks.)
 #pragma once
 
@@ -106,6 +108,16 @@ const V* find_by_name(const V* (*table)(int*), const char* name) {
     const V* all = table(&n);
     for (int i = 0; i < n; ++i)
         if (std::strcmp(all[i].name, name) == 0) return &all[i];
+    return nullptr;
+}
+
+// The entry of a sibling stage's table with a profile's shape (align and split run on the domain stage's variant).
+template <class V>
+const V* find_by_shape(const V* (*table)(int*), int S, bool isc) {
+    int n = 0;
+    const V* all = table(&n);
+    for (int i = 0; i < n; ++i)
+        if (all[i].S == S && all[i].isc == isc) return &all[i];
     return nullptr;
 }
 
@@ -277,16 +289,21 @@ using LaunchFn = msv_status (*)(P*, const uint8_t*, const uint64_t*, uint64_t, c
 // previous launch ran on another stream is reused only after it: launch_ring.h), so launches of one profile on
 // several streams never share a counter; a slot's counters are put back to zero by the last wave of every launch,
 // and a failed launch may leave them dirty, so the slot's next launch resets them explicitly (LaunchRing::run).
-// enqueue(blocks, counter) launches the kernel on `st`.
+// enqueue(blocks, counter) launches the kernel on `st`; `grid` is the persistent grid of that kernel (the profile's
+// own kernel: p->blocks).
 template <class Enqueue>
-msv_status run(StageProfile* p, hipStream_t st, uint64_t n, uint64_t per_block, Enqueue enqueue) {
+msv_status run(StageProfile* p, hipStream_t st, uint64_t n, uint64_t per_block, uint32_t grid, Enqueue enqueue) {
     if (n == 0) return MSV_OK;
     if (n >= (1ull << 32)) return MSV_ERR_INVALID_ARGUMENT;
     const uint64_t need = (n + per_block - 1) / per_block;
-    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(p->blocks, need));
+    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(grid, need));
     MSV_HIP(p->kernels.run(st, lazy(p, st), p->d_words.get(), 2,
                            [&](uint32_t* counter) { return enqueue(blocks, counter); }));
     return MSV_OK;
+}
+template <class Enqueue>
+msv_status run(StageProfile* p, hipStream_t st, uint64_t n, uint64_t per_block, Enqueue enqueue) {
+    return run(p, st, n, per_block, p->blocks, enqueue);
 }
 
 template <class P>

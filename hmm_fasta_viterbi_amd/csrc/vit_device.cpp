@@ -132,11 +132,7 @@ msv_status msv_vit_profile_describe(const msv_vit_profile* p, msv_vit_info* out)
     out->max_length = p->lentab_n ? p->lentab_n - 1 : 0;
     out->device = p->device;
     std::snprintf(out->variant, sizeof(out->variant), "%s", p->v->name);
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, p->v->fn) == hipSuccess) {
-        out->scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        out->lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);  // the kernel's own static LDS, exactly
-    }
+    msvrt::kernel_footprint(p->v->fn, &out->scratch_bytes, &out->lds_bytes);  // (the kernel's own static LDS)
     return MSV_OK;
 }
 

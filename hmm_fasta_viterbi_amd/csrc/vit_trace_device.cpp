@@ -1,9 +1,10 @@
 // vit_trace_device.cpp -- C-ABI of the Viterbi trace (msv.h "Viterbi traces") on the HIP runtime.
 //
 // msv_vit_trace_batch stages the batch like the other host calls (the profile's CsrStaging, a StreamDrain on
-// early returns), cuts the select list into chunks whose back-pointers fit the workspace (vit_trace_plan.cpp),
-// and per chunk runs the fill kernel on a launch slot of the profile, the walk's counting pass, an exclusive
-// scan of the counts on the host (the output is sized exactly from it), and the walk's writing pass.
+// early returns), lays the select list out in chunks whose back-pointers fit the workspace (item_plan.h's
+// chunk_layout over vit_trace_plan.cpp's cuts), and per chunk runs the fill kernel on a launch slot of the profile,
+// the walk's counting pass, an exclusive scan of the counts on the host (the output is sized exactly from it), and
+// the walk's writing pass.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,23 +59,17 @@ msv_status ensure_plan(msv_vit_profile* p) {
 // The host lists a chunk's copies read or write: owned by the call, so that they outlive the stream's drain on
 // an early return.
 struct ChunkLists {
-    std::vector<uint64_t> base, dom_off, ops_off;
+    std::vector<uint64_t> dom_off, ops_off;
     std::vector<uint32_t> counts;
 };
 
-// One chunk: the select entries sel[0 .. m) with their workspace sizes, appended to `out` at entry `first`.
-msv_status run_chunk(msv_vit_profile* p, const uint32_t* sel, const uint64_t* bytes, uint64_t m, uint64_t first,
-                     hipStream_t st, ChunkLists& h, msv_vit_traces* out) {
+// One chunk: the select entries sel[0 .. m), each from word base[j] of the chunk's `words`, appended to `out` at
+// entry `first`.
+msv_status run_chunk(msv_vit_profile* p, const uint32_t* sel, const uint64_t* base, uint64_t words, uint64_t m,
+                     uint64_t first, hipStream_t st, ChunkLists& h, msv_vit_traces* out) {
     vitdev::TraceState& t = p->trace;
     const vittrace::Plan& pl = vittrace::kPlans[t.plan];
     msvrt::CsrStaging& sg = p->staged;
-    std::vector<uint64_t>& base = h.base;
-    base.assign(m, 0);
-    uint64_t words = 0;
-    for (uint64_t j = 0; j < m; ++j) {
-        base[j] = words;
-        words += bytes[j] / sizeof(uint32_t);
-    }
     MSV_HIP(t.d_select.reserve(m));
     MSV_HIP(t.d_base.reserve(m));
     MSV_HIP(t.d_counts.reserve(2 * m));
@@ -82,7 +77,7 @@ msv_status run_chunk(msv_vit_profile* p, const uint32_t* sel, const uint64_t* by
     MSV_HIP(t.d_dom_off.reserve(m + 1));
     MSV_HIP(t.d_ops_off.reserve(m + 1));
     MSV_HIP(hipMemcpyAsync(t.d_select, sel, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    MSV_HIP(hipMemcpyAsync(t.d_base, base.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    MSV_HIP(hipMemcpyAsync(t.d_base, base, m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
 
     vittrace::FillArgs f{};
     f.etab = t.d_etab;
@@ -129,11 +124,8 @@ msv_status run_chunk(msv_vit_profile* p, const uint32_t* sel, const uint64_t* by
     MSV_HIP(hipMemcpyAsync(counts.data(), t.d_counts, 2 * m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipMemcpyAsync(out->scores.data() + first, t.d_scores, m * sizeof(float), hipMemcpyDeviceToHost, st));
     MSV_HIP(hipStreamSynchronize(st));
-    float ms = 0;
-    MSV_HIP(hipEventElapsedTime(&ms, t.t0, t.t1));
-    out->stats.fill_ms += ms;
-    MSV_HIP(hipEventElapsedTime(&ms, t.t2, t.t3));
-    out->stats.walk_ms += ms;
+    out->stats.fill_ms += msvrt::elapsed(t.t0, t.t1);
+    out->stats.walk_ms += msvrt::elapsed(t.t2, t.t3);
     out->stats.chunks += 1;
     out->stats.pointer_bytes += words * sizeof(uint32_t);
 
@@ -167,8 +159,7 @@ msv_status run_chunk(msv_vit_profile* p, const uint32_t* sel, const uint64_t* by
                            st));
     MSV_HIP(hipMemcpyAsync(out->ops.data() + o0, t.d_ops, no, hipMemcpyDeviceToHost, st));
     MSV_HIP(hipStreamSynchronize(st));
-    MSV_HIP(hipEventElapsedTime(&ms, t.t2, t.t3));
-    out->stats.walk_ms += ms;
+    out->stats.walk_ms += msvrt::elapsed(t.t2, t.t3);
     for (uint64_t d = d0; d < d0 + nd; ++d) out->domains[d].ops_begin += o0;
     return MSV_OK;
 }
@@ -216,18 +207,14 @@ msv_status msv_vit_trace_batch(msv_vit_profile* p, const uint8_t* residues, cons
     if ((s = msv_vit_profile_reserve_length(p, longest)) != MSV_OK) return fail(s);
     const vittrace::Plan& pl = vittrace::kPlans[p->trace.plan];
     // the chunk cuts, before anything is launched: a sequence that alone exceeds the workspace is refused here
-    std::vector<uint64_t> bytes(ns), cuts;
+    std::vector<uint64_t> bytes(ns);
     for (uint64_t q = 0; q < ns; ++q)
         bytes[q] = vittrace::sequence_words(pl, offsets[sel[q] + 1] - offsets[sel[q]]) * sizeof(uint32_t);
-    const uint64_t workspace = workspace_bytes ? workspace_bytes : vittrace::kDefaultWorkspace;
-    if (!vittrace::chunk_cuts(bytes.data(), ns, workspace, &cuts)) return fail(MSV_ERR_OUT_OF_MEMORY);
-    uint64_t most = 0;
-    for (size_t c = 0; c + 1 < cuts.size(); ++c) {
-        uint64_t sum = 0;
-        for (uint64_t q = cuts[c]; q < cuts[c + 1]; ++q) sum += bytes[q];
-        most = std::max(most, sum);
-    }
-    hipError_t e = p->trace.d_ws.reserve(most / sizeof(uint32_t));
+    itemplan::ChunkLayout lay;  // in words
+    if (!itemplan::chunk_layout(bytes.data(), ns, workspace_bytes, sizeof(uint32_t), 0, &lay))
+        return fail(MSV_ERR_OUT_OF_MEMORY);
+    const std::vector<uint64_t>& cuts = lay.cuts;
+    hipError_t e = p->trace.d_ws.reserve(lay.chunk_units);
     if (e != hipSuccess) return fail(hip_status(e));
     hipStream_t st = p->stream;
     ChunkLists lists;
@@ -236,9 +223,11 @@ msv_status msv_vit_trace_batch(msv_vit_profile* p, const uint8_t* residues, cons
         msvrt::StreamDrain drain(st);
         e = p->staged.upload(residues, offsets, 0, n, true, st, st);
         s = hip_status(e);
-        for (size_t c = 0; s == MSV_OK && c + 1 < cuts.size(); ++c)
-            s = run_chunk(p, sel.data() + cuts[c], bytes.data() + cuts[c], cuts[c + 1] - cuts[c], cuts[c], st,
-                          lists, out);
+        for (size_t c = 0; s == MSV_OK && c + 1 < cuts.size(); ++c) {
+            const uint64_t last = cuts[c + 1] - 1, words = lay.base[last] + bytes[last] / sizeof(uint32_t);
+            s = run_chunk(p, sel.data() + cuts[c], lay.base.data() + cuts[c], words, cuts[c + 1] - cuts[c], cuts[c],
+                          st, lists, out);
+        }
     }  // (drained: every chunk has synchronised, or an error has)
     p->trace.d_ws.reset();  // the workspace is not kept between calls
     if (s != MSV_OK) return fail(s);
@@ -285,11 +274,7 @@ msv_status msv_vit_trace_describe(msv_vit_profile* p, msv_vit_trace_info* out) {
     out->words_per_lane = pl.words();
     out->blocks = p->trace.blocks;
     out->default_workspace_bytes = vittrace::kDefaultWorkspace;
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, vittrace::fill_kernel(p->trace.plan)) == hipSuccess) {
-        out->scratch_bytes = static_cast<uint32_t>(fa.localSizeBytes);
-        out->lds_bytes = static_cast<uint32_t>(fa.sharedSizeBytes);
-    }
+    msvrt::kernel_footprint(vittrace::fill_kernel(p->trace.plan), &out->scratch_bytes, &out->lds_bytes);
     return MSV_OK;
 }
 

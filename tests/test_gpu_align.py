@@ -262,6 +262,39 @@ def test_more_items_than_resident_waves(name):
         assert again["ops"].tobytes() == deep["ops"].tobytes()
 
 
+SHARED_LENGTHS = (30, 47, 80, 64, 55)
+# two overlapping items on sequence 3, one of a single residue, two whole sequences; not in sequence order
+SHARED_ITEMS = [(3, 10, 50), (0, 1, 30), (3, 30, 64), (1, 17, 17), (4, 5, 40), (2, 1, 80)]
+
+
+def shared_batch(isc):
+    """100.hmm's tables, five sequences of 30 to 80 residues and SHARED_ITEMS on them."""
+    hmm = msv.Profile_HMM(os.path.join(ROOT, "data", "profile_HMMs", "100.hmm"))
+    model = forward_lib.tables(hmm, 1 if isc else 0)
+    codes, offsets = _csr([stretch(model, L, 800 + L) for L in SHARED_LENGTHS])
+    return model, codes, offsets, list(SHARED_ITEMS)
+
+
+@pytest.mark.parametrize("name", VARIANTS)
+def test_item_order_and_shared_sequences(name):
+    """An item's bytes do not depend on the items around it: each of SHARED_ITEMS alone against one call over all of
+    them whose workspace holds two of the largest, so that the call runs in several chunks."""
+    S, isc = shape_of(name)
+    model, codes, offsets, items = shared_batch(isc)
+    nbytes = [int(_native.lib().msv_aln_item_bytes(S, b - a + 1)) for _, a, b in items]
+    with Profile(model, name) as p:
+        batch = p.align(codes, offsets, items, keep=False, workspace_bytes=2 * max(nbytes))
+        assert batch["stats"]["chunks"] > 1 and len(batch["env"]) == len(items)
+        assert np.all(np.isfinite(batch["env"])) and len(batch["domains"]) >= 1
+        for q, item in enumerate(items):
+            alone = p.align(codes, offsets, [item], keep=False)
+            assert alone["stats"]["chunks"] == 1
+            assert bits(batch["env"][q:q + 1]) == bits(alone["env"]), (q, item)
+            assert bits(batch["oa"][q:q + 1]) == bits(alone["oa"]), (q, item)
+            for x, y in zip(item_domains(batch, q), item_domains(alone, 0)):
+                assert x.tobytes() == y.tobytes(), (q, item)
+
+
 def test_error_classes():
     S, isc = 6, False
     model = base_model(64 * S, 31, isc)

@@ -249,6 +249,26 @@ def test_more_items_than_resident_waves(name):
         check_items(p, codes, offsets, pick, f"split deep queue {name}")
 
 
+@pytest.mark.parametrize("name", VARIANTS)
+def test_item_order_and_shared_sequences(name):
+    """An item's bytes do not depend on the items around it: each of test_gpu_align's SHARED_ITEMS alone against one
+    call over all of them, same seed, whose workspace holds two of the largest, so that it runs in several chunks."""
+    from test_gpu_align import shared_batch
+    S, isc = shape_of(name)
+    model, codes, offsets, items = shared_batch(isc)
+    nbytes = [int(_native.lib().msv_spl_item_bytes(S, b - a + 1)) for _, a, b in items]
+    with Profile(model, name) as p:
+        batch = p.sample(codes, offsets, items, workspace_bytes=2 * max(nbytes))
+        assert batch["stats"]["chunks"] > 1 and len(batch["env"]) == len(items)
+        assert np.all(np.isfinite(batch["env"])) and len(batch["segments"]) >= 1
+        for q, item in enumerate(items):
+            alone = p.sample(codes, offsets, [item])
+            assert alone["stats"]["chunks"] == 1
+            assert bits(batch["env"][q:q + 1]) == bits(alone["env"]), (q, item)
+            x, y = item_segments(batch, q, NS), item_segments(alone, 0, NS)
+            assert np.array_equal(x[0], y[0]) and x[1].tobytes() == y[1].tobytes(), (q, item)
+
+
 def test_error_classes():
     S, isc = 6, False
     model = base_model(64 * S, 31, isc)
